@@ -1,10 +1,17 @@
 """Headline benchmark: Msamples/s of the gfx950 path tracer on scenes/scene_08.json at
 1920x1080, 256 spp, 8 bounces (BASELINE.json config 3), 1..8 GPUs.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
     FR_BENCH_DEVICES=0,0 python bench.py --gpus 2     (rehearsal: two shards on device 0)
+
+A plain run does only what the headline needs: set-up, W warm-up frames, the K timed frames,
+the outputs of the last timed frame if --dump-outputs is given, and the JSON line (with the
+rooflines' algorithmic side, which costs no run of its own: the timed frames' own counters
+and HIP events). --full adds the measurements that take runs of their own: the rocprofv3
+counter passes (--no-pmc drops them), the CPU baseline with config C1 (--no-cpu-baseline
+drops it), and at N > 1 the whole frame rendered on one device to check the stitched one.
 
 Two ways to run N > 1 (launch_plan): a plain `python bench.py --gpus N` drives devices
 0..N-1 from this one process through fr_mctx, the drop-in's multi-device context
@@ -26,12 +33,17 @@ Rank 0 prints one JSON line with:
 - frame_span_ms: a frame's trace start to its sum's end (frames overlap when streamed);
 - roofline: the trace kernel's binding bound, FP32 VALU: algorithmic FLOP/s (constants
   frozen in fo-rma_amd/csrc/flops.h, times the kernel's exact counters) against the
-  157.3 TFLOP/s peak, plus the VALU issue fraction and HBM traffic read from rocprofv3
-  hardware counters in this run (a child process, N=1 only);
+  157.3 TFLOP/s peak, plus (--full) the VALU issue fraction and HBM traffic read from
+  rocprofv3 hardware counters in this run (a child process, N=1 only);
 - hbm_roofline: algorithmic bytes per launch against 8 TB/s (the north star's ask);
-- cpu_baseline (N=1): the oracle on this host's cores, all of them and one; its `c1`
+- cpu_baseline (--full, N=1): the oracle on this host's cores, all of them and one; its `c1`
   entry is BASELINE config C1 (scene_01 256x256/4 spp/4 bounces, the reference's CPU
   case) in full on the oracle (1 thread, all threads) and on the GPU, compared bit for bit.
+
+--dump-outputs DIR writes what a caller of the timed path receives from the last timed frame,
+after the timed region: DIR/mean.npy ([H, W, 3] f32 means), DIR/u8.npy (the [H, W, 3] u8
+image, stored as float32) and DIR/counters.npy (float64: samples, segments, hits, scatters
+of the frame). The scene, camera and seed are fixed, so two builds compare output for output.
 """
 import argparse
 import glob
@@ -501,6 +513,19 @@ def frame_hash(mean):
     return hashlib.sha256(mean.tobytes()).hexdigest()[:16]
 
 
+def dump_outputs(path, mean, u8, counts):
+    """--dump-outputs: the last timed frame as a caller receives it, one .npy per array:
+    the f32 means, the u8 image (as float32) and the frame's exact counters (float64).
+    1920x1080: 2 x 24.9 MB, so nothing is sampled."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "mean.npy"), np.asarray(mean, dtype=np.float32))
+    np.save(os.path.join(path, "u8.npy"), np.asarray(u8).astype(np.float32))
+    np.save(os.path.join(path, "counters.npy"),
+            np.array([counts[k] for k in ("samples", "segments", "hits", "scatters")], dtype=np.float64))
+
+
 def compare_with_n1(stitched, n1):
     """The N > 1 line's self-check: the frame stitched from the N shards against the same
     frame rendered whole on one device (the RNG is keyed by global pixel, so the strips of
@@ -594,7 +619,7 @@ def run_mctx(a, plan, torch, fr):
                        if launches_ms else None,
                        "frame_span_ms": round(sum(frames_ms) / max(1, len(frames_ms)), 4),
                        "launches_logged": len(launches_ms)})
-    mean, _ = mc.frame()
+    mean, u8 = mc.frame()
     value = total["samples"] * a.steps / elapsed / 1e6
     slow = max(shards, key=lambda s: s["trace_ms_per_launch"] * s["trace_launches"])
     launches = max(1, slow["trace_launches"])
@@ -628,7 +653,12 @@ def run_mctx(a, plan, torch, fr):
         "hbm_roofline": hbm,
     })
     mc.close()
-    out.update(compare_with_n1(mean, render_n1_frame(fr, devices[0], scene, cam, a.no_scene_jit)))
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, mean, u8, total)
+    # every line reports its stitched frame's hash; --full renders the whole frame on one
+    # device as well (a run of its own) and checks the stitched one against it
+    out.update(compare_with_n1(mean, render_n1_frame(fr, devices[0], scene, cam, a.no_scene_jit)) if a.full
+               else {"frame_sha256_16": frame_hash(mean)})
     return out
 
 
@@ -687,15 +717,20 @@ def run_rank(a, plan, torch, fr):
     pixels = len(shard_rows(HEIGHT, rank, world)) * WIDTH
 
     # every run reports its frame's hash; N > 1 stitches the shards on rank 0 (after the timed
-    # region) and checks them against the whole frame rendered on rank 0's device
+    # region), and --full checks them against the whole frame rendered on rank 0's device
     frame_img = gather_frame(frame.mean, rank, world, HEIGHT)
+    frame_u8 = gather_frame(frame.u8, rank, world, HEIGHT) if a.dump_outputs else None
     check = None
     if rank == 0:
-        check = ({"frame_sha256_16": frame_hash(frame_img)} if world == 1 else
+        check = ({"frame_sha256_16": frame_hash(frame_img)} if world == 1 or not a.full else
                  compare_with_n1(frame_img, render_n1_frame(fr, local, scene, cam, a.no_scene_jit)))
+    if a.dump_outputs:
+        last = {k: barrier.sum(stats[-1][k]) for k in ("samples", "segments", "hits", "scatters")}
+        if rank == 0:
+            dump_outputs(a.dump_outputs, frame_img, frame_u8, last)
     if rank != 0:
         return None
-    pmc = pmc_in_run(scene_jit=jit["used"]) if (world == 1 and not a.no_pmc) else {}
+    pmc = pmc_in_run(scene_jit=jit["used"]) if (a.full and world == 1 and not a.no_pmc) else {}
     issue = valu_issue(pmc)
     traffic = hbm_traffic(pmc)
     value = total_samples / elapsed / 1e6
@@ -734,7 +769,7 @@ def run_rank(a, plan, torch, fr):
     if pmc:
         out["pmc"] = pmc
     out.update(check)
-    if world == 1 and not a.no_cpu_baseline:
+    if a.full and world == 1 and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(a.cpu_budget)
         out["speedup_vs_cpu_baseline"] = round(value / out["cpu_baseline"]["value"], 1)
         try:
@@ -754,12 +789,17 @@ def parse_args(argv=None):
     # frames' sums are inside the timed region too
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 counter passes")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the last timed frame's outputs as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what takes runs of its own: the rocprofv3 counter passes, the CPU baseline "
+                         "with config C1, and at N > 1 the N = 1 frame the stitched one is checked against")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-pmc", action="store_true", help="with --full: skip the rocprofv3 counter passes")
     ap.add_argument("--cpu-budget", type=float, default=12.0)
     ap.add_argument("--verify", action="store_true",
-                    help="(kept for old command lines: every run now reports its frame hash, and N > 1 checks it "
-                         "against the N = 1 frame)")
+                    help="(kept for old command lines: every run now reports its frame hash, and N > 1 with "
+                         "--full checks it against the N = 1 frame)")
     ap.add_argument("--sync-each", action="store_true", help="wait for each frame's stats before the next")
     ap.add_argument("--no-scene-jit", action="store_true",
                     help="run the compiled-in trace kernel instead of the scene-specialised one (same image)")
@@ -768,6 +808,8 @@ def parse_args(argv=None):
 
 def main():
     a = parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        raise SystemExit(f"bench.py: --steps must be >= 1 and --warmup >= 0, got {a.steps} and {a.warmup}")
     plan = launch_plan(a.gpus)
     import torch
 

@@ -51,6 +51,29 @@ def test_parse_args_driver_command_line():
     assert (a.gpus, a.steps, a.warmup) == (1, 20, 2)
 
 
+def test_parse_args_plain_run_is_lean_by_default():
+    a = bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert (a.full, a.dump_outputs) == (False, None)
+    a = bench.parse_args(["--full", "--dump-outputs", "d", "--no-pmc"])
+    assert (a.full, a.dump_outputs, a.no_pmc, a.no_cpu_baseline) == (True, "d", True, False)
+
+
+def test_dump_outputs_writes_the_frame_as_float_arrays(tmp_path):
+    import numpy as np
+    mean = np.linspace(0.0, 1.0, 4 * 5 * 3, dtype=np.float32).reshape(4, 5, 3)
+    u8 = (mean * 255).astype(np.uint8)
+    counts = {"samples": 80, "segments": 2 ** 33 + 1, "hits": 7, "scatters": 5, "occupancy": 4}
+    d = tmp_path / "out" / "dump"
+    bench.dump_outputs(str(d), mean, u8, counts)
+    assert sorted(p.name for p in d.iterdir()) == ["counters.npy", "mean.npy", "u8.npy"]
+    got = np.load(d / "mean.npy")
+    assert got.dtype == np.float32 and np.array_equal(got.view(np.uint32), mean.view(np.uint32))
+    got = np.load(d / "u8.npy")
+    assert got.dtype == np.float32 and got.shape == (4, 5, 3) and np.array_equal(got, u8)
+    got = np.load(d / "counters.npy")
+    assert got.dtype == np.float64 and got.tolist() == [80, 2 ** 33 + 1, 7, 5]
+
+
 def test_frame_hash_is_the_rehearsal_checksum():
     import numpy as np
     m = np.zeros((4, 5, 3), np.float32)

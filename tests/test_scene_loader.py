@@ -13,7 +13,8 @@ from oracle import scene_ref as S
 
 SCENES_OK = ["scene_01", "scene_02", "scene_03", "scene_04", "scene_05", "scene_06", "scene_07", "scene_08",
              "scene_09"]
-REF_SCENES = "/root/reference/scenes"
+# the reference's scenes/*.json as published, byte for byte (fixtures)
+REF_SCENES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_scenes")
 
 
 def _same(prims_c, prims_ref):
@@ -44,7 +45,6 @@ def test_scene08_slabs(fr):
     assert list(pr[2].g[:6]) == [0.0, np.float32(-30.05), -35.0, 60.0, np.float32(-29.95), 35.0]
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_SCENES), reason="reference checkout not present (GPU box)")
 def test_bundled_scenes_parse_like_the_reference_files(fr):
     for name in SCENES_OK:
         a = json.load(open(os.path.join(REF_SCENES, f"{name}.json")))
