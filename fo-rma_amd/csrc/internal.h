@@ -13,7 +13,7 @@ namespace fr {
 // thread-local last-error message behind fr_last_error()
 int set_error(int code, const char* fmt, ...);
 
-struct DeviceCopy;  // defined in render.hip
+struct DeviceCopy;  // defined in render.hip (the upload of pack.h's blob)
 
 }  // namespace fr
 

@@ -8,10 +8,7 @@
 
 namespace fr {
 
-// List-loop scenes up to this many primitives may be compiled into the kernel: the
-// unrolled list stays within a few KB of code, and every record is staged in LDS
-// (kRecLds) for the winner's shading as in the list kernels.
-constexpr uint32_t kJitMaxPrims = 64;
+// (which scenes ask for it: plan.h, kJitMaxPrims and FramePlan::jit_on)
 
 struct JitSpec {
   const char* name_expr;   // "fr::trace_kernel<KS, HP, ...>": the launch's specialisation

@@ -1,0 +1,161 @@
+// kparams.h — the launch contract the host driver and the device code share: block and
+// tile sizes, the KParams flag bits, the sample-buffer and LDS layout constants, the
+// kernel-selection tuning values, KParams itself and the invariant division it carries.
+//
+// Host-safe: compiles under g++ with no HIP headers (plan.cpp, pack.cpp), under hipcc
+// (trace_kernel.h, sum.h) and under hiprtc (the run-time build of trace_kernel.h).
+#pragma once
+#include <stdint.h>
+
+#if defined(__HIPCC_RTC__) || defined(__HIPCC__) || defined(__HIP__)
+#define FR_KHD __host__ __device__ __forceinline__
+#define FR_KHD_CONSTEXPR __host__ __device__ constexpr
+#else
+#define FR_KHD static inline
+#define FR_KHD_CONSTEXPR constexpr
+#endif
+
+namespace fr {
+
+constexpr uint32_t kBlock = 256;      // 4 waves, one 8x8 pixel tile each
+constexpr uint32_t kStripRows = 8;    // rows per shard strip == tile height
+constexpr uint32_t kMaxDepth = 64;    // LDS stack bound (64 KB per workgroup)
+constexpr uint32_t kMaxWgPerCu = 8;   // 2048 threads per CU / kBlock: the persistent grid's cap
+#ifndef FR_KREJ
+#define FR_KREJ 4  // rejection loop: lanes left to the next iteration (tuning only, results unchanged)
+#endif
+// ... for the 8-B-record kernels (scenes of <= 15 primitives, the headline's): measured
+// C3 trace 20.81 -> 20.69 ms at 6 (7 and 8 the same within noise); 6 on the other kernels
+// cost C2 +1.7 % and a 10k-sphere BVH frame +1.2 %, so they keep FR_KREJ
+// Re-tuned for the scene-specialised kernel (round 3): 9 with
+// FR_CLAIM_MIN_NIB 3 streams C3 at 16.49 ms per frame against 16.63 (6 / 2), three runs;
+// shard 0/8 unchanged (tools/gpu_knob_shards.sh, profiles/r03k_knob_shards.log)
+#ifndef FR_KREJ_NIB
+#define FR_KREJ_NIB 9
+#endif
+// ... for the BVH kernels with 8-B attenuation-class records: C5 trace 39.51 -> 39.17 ms at 2
+// (0: 39.87, 1: 39.27, 3: 39.31, 6: 40.14; profiles/r06af_ab_c5_krej.log, four runs)
+#ifndef FR_KREJ_BVH
+#define FR_KREJ_BVH 2
+#endif
+constexpr uint32_t kSmallDepth = 8;
+// Deferred unwind (DEFER kernels: depth <= 8, <= kDeferMaxPrims primitives, no BVH, not
+// render_mt): a path's sample slot holds the record {t, winners 0-3, winners 4-7} instead
+// of its colour: t = the sky blend parameter 0.5 (unit(d).y + 1) of the escaping ray, or
+// kDeferAbsorbed (-1, which no t in [0, 1] or NaN equals) for a path that returns 0; the
+// winners as u8 primitive indices, kDeferUnit on empty levels. sum_kernel rebuilds
+// a0 * (a1 * (... * term)) from it in the same order, at full SIMD width instead of in the
+// few lanes whose paths end in a given iteration.
+constexpr uint32_t kDeferMaxPrims = 254;
+constexpr uint32_t kDeferUnit = 255;
+constexpr uint32_t kDeferAbsorbed = 0xBF800000u;  // -1.0f
+constexpr uint32_t KF_DEFER = 1u << 31;            // internal KParams.flags bit: records, not colours
+constexpr uint32_t KF_STAGE = 1u << 30;            // internal: BVH kernel stages its samples in LDS
+// Scenes of <= kNibbleMaxPrims primitives (the headline scene_08 has 6) keep the winners
+// as 4-bit entries in one register instead of an LDS stack (15 = empty level) and store
+// 8-B records {t, winners}: 2 words per sample instead of 3 (KF_NIBBLE, DEFER == 2).
+constexpr uint32_t kNibbleMaxPrims = 15;
+constexpr uint32_t kNibbleUnit = 15;
+constexpr uint32_t KF_NIBBLE = 1u << 29;           // internal: 8-B deferred records
+constexpr uint32_t KF_DIFFUSE = 1u << 28;          // internal: no metal/dielectric (trace_kernel MAT = 1)
+// FR_SKY_DEFER builds (A/B): the 8-B-record kernel stores 12-B records {d.y, dot(d, d),
+// winners} and sum_kernel computes the sky parameter, at full SIMD width, instead of the
+// trace kernel in the few lanes whose path escapes in a given iteration. dot(d, d) = -1
+// (which no sum of squares is) marks an absorbed path.
+#ifdef FR_SKY_DEFER
+constexpr bool kSkyDefer = true;
+#else
+constexpr bool kSkyDefer = false;
+#endif
+#ifndef FR_BLOCK_SAMPLES
+#define FR_BLOCK_SAMPLES 16  // RNG contract: one stream per 16-sample block (oracle.cpp agrees)
+#endif
+constexpr uint32_t kBlockSamples = FR_BLOCK_SAMPLES;  // samples per RNG stream (numerics contract)
+// The last block of a pixel with more than one block is split into sub-blocks of
+// kFineSamples samples, each its own stream (key kFineKey | s / kFineSamples): the queue
+// ends with short items, so the drain after the last claim is short.
+// (Splitting the last 2, 3 or 4 blocks measured 0.9-2.7 % slower at 1 GPU for 1-2 % at
+// shard 0 of 8; one queue head per XCD, with stealing, 1.4 % slower.)
+#ifndef FR_FINE_SAMPLES
+#define FR_FINE_SAMPLES 4
+#endif
+constexpr uint32_t kFineSamples = FR_FINE_SAMPLES;
+constexpr uint32_t kFineSub = kBlockSamples / kFineSamples;  // sub-blocks per block
+constexpr uint32_t kFineKey = 0x80000000u;
+static_assert(kFineSamples >= 1 && kBlockSamples % kFineSamples == 0 && kFineSub <= 4,
+              "sub-block index packs into 2 bits of the claim's block word");
+
+// KS: KS_AABB / KS_SPHERE when every primitive has that kind (no per-primitive kind
+// switch), else KS_ANY (trace_kernel's first template argument).
+enum { KS_ANY = 0, KS_AABB = 1, KS_SPHERE = 2 };
+
+struct KParams {
+  uint32_t W, H, spp, max_depth;
+  uint64_t seed;
+  uint32_t shard_index, shard_count, tiles_per_row, n_tiles, flags;
+  uint32_t P;         // pixel slots of the shard: n_tiles x 64, tile order
+  uint32_t b0, nb;    // this pass renders sample blocks [b0, b0 + nb)
+  uint32_t n_items;   // nb x P work items (pixel slot, block); < 2^32 per pass
+  uint32_t tiles_magic, tiles_shift;  // x / n_tiles = fastdiv(x, tiles_magic, tiles_shift)
+  // the jitter's (x + r) / W as 2^24 (x + r) / (2^24 W), the 2^24 folded into the operands
+  // (exact scalings): rW = RN(1 / W) 2^-24 = RN(1 / (2^24 W)) (host IEEE division), sW =
+  // 2^24 W; the same for H
+  float rW, rH, sW, sH;
+  uint32_t row_magic, row_shift;      // x / tiles_per_row = fastdiv(x, row_magic, row_shift)
+  uint32_t band_h;                    // FR_FLAG_MT_BANDS: rows per band, H / 4 (tracer.rs:87)
+  uint32_t ks;          // sample slots per work item in the sample buffer: min(spp, kBlockSamples)
+  // items handed out without the queue: wave w of the grid starts on batch w (one batch
+  // per wave, n_static = waves x 64); the queue counts from n_static
+  uint32_t n_static;
+  // items [n_coarse, n_items) are the sub-blocks of block b_fine (the pixels' last block,
+  // when spp > kBlockSamples and this pass holds it): item = n_coarse + k * P + q for
+  // sub-block k; n_coarse = n_items when the pass has none
+  uint32_t n_coarse, b_fine;
+};
+
+// Unsigned 32-bit division by the invariant n_tiles: q = (t + ((x - t) >> s1)) >> s2 with
+// t = mulhi(x, m), l = ceil(log2 d), m = floor(2^32 (2^l - d) / d) + 1, s1 = min(l, 1),
+// s2 = max(l - 1, 0) (Granlund-Montgomery; d = 1 gives m = 1, q = x). tests/test_fastdiv.py.
+FR_KHD uint32_t fastdiv(uint32_t x, uint32_t m, uint32_t shifts) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const uint32_t t = __umulhi(x, m);
+#else
+  const uint32_t t = static_cast<uint32_t>((static_cast<uint64_t>(x) * m) >> 32);
+#endif
+  return (t + ((x - t) >> (shifts & 1u))) >> (shifts >> 1);
+}
+
+// The host's half: m and the packed shifts (s1 | s2 << 1) for the divisor d.
+static inline void fastdiv_magic(uint32_t d, uint32_t& m, uint32_t& shifts) {
+  if (d < 1) d = 1;
+  const uint32_t l = d == 1 ? 0u : 32u - static_cast<uint32_t>(__builtin_clz(d - 1));
+  m = static_cast<uint32_t>(((static_cast<uint64_t>(1) << 32) * ((static_cast<uint64_t>(1) << l) - d)) / d + 1);
+  shifts = (l < 1 ? l : 1u) | ((l > 0 ? l - 1 : 0u) << 1);
+}
+
+constexpr uint32_t kAttLds = 1024;  // attenuation/class entries staged in LDS (16 B each)
+constexpr uint32_t kRecLds = 64;    // whole 64-B records staged in LDS for small scenes
+// Sample colours a lane stages in LDS before storing them to the (item-major) sample
+// buffer: 4 x 12 B = three 16-B stores per 4 samples (4 x 8 B = two, for 8-B records)
+// instead of four scattered stores, which L2 wrote back as partial lines (3.5x WRITE_SIZE).
+// The BVH kernels stage 2 samples when their LDS allows (below).
+#ifndef FR_STAGE
+#define FR_STAGE 4  // 1 or 4 (A/B builds)
+#endif
+// The BVH kernels stage 2 samples when the 6 KB this adds to their LDS (which holds the
+// traversal stack) keeps their resident workgroups per CU (KF_STAGE, decided at launch):
+// C5 66.8 -> 64.3 ms; on scenes whose LDS tables fill the CU it would cost a workgroup.
+#ifndef FR_BVH_STAGE
+#define FR_BVH_STAGE 2
+#endif
+// (BVH kernels with 8-B records stage like the list kernels: their LDS holds no unwind stack)
+FR_KHD_CONSTEXPR uint32_t stage_samples(bool bvh, bool nib = false) {
+  return bvh && !nib ? FR_BVH_STAGE : FR_STAGE;
+}
+// FR_BVH_RSTAGE=1: the BVH kernels hold a pair's first colour in registers instead of LDS
+// (3 VGPRs, none of the traversal stack's LDS), so every BVH launch stores whole pairs.
+#ifndef FR_BVH_RSTAGE
+#define FR_BVH_RSTAGE 0
+#endif
+
+}  // namespace fr

@@ -69,7 +69,7 @@ FR_HD float schlick(float cosine, float ref_idx) {
 // ---------------------------------------------------------------------------
 // RNG. One stream per (seed, pixel, key): key b for block b of 16 samples, and, when
 // spp > 16, 2^31 | s / 4 for the 4-sample sub-blocks of the pixel's last block
-// (render.hip stream_key). splitmix64 keys a xoshiro128+ 1.0 state (Blackman & Vigna's
+// (trace_kernel.h stream_key). splitmix64 keys a xoshiro128+ 1.0 state (Blackman & Vigna's
 // generator for floating-point output: only the upper bits are used); a stream's
 // samples draw from it in sample order (the reference's save_image draws every sample
 // from one sequential stream, tracer.rs:164-175). f32 = ((u32 ^ 2^31) >> 8) * 2^-24.
@@ -182,7 +182,7 @@ FR_HD V3 random_in_unit_sphere(Rng& r) {
 // shapes/sphere.rs:23-51 without the record writes; a = dot(d, d) (loop-invariant).
 // Both roots are formed unconditionally (no side effects) and the near one wins.
 // rr = RN(radius * radius), the product the test forms (the BVH's leaf records carry it in
-// place of the radius, render.hip)
+// place of the radius, pack.cpp)
 FR_HD bool sphere_root_rr(V3 c, float rr, V3 o, V3 d, float a, float t_min, float t_max, float& t) {
   const V3 oc = sub(o, c);
   const float b = dot(oc, d);

@@ -5,7 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "trace_kernel.h"
+#include "kparams.h"
 
 namespace fr {
 

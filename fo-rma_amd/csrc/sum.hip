@@ -2,6 +2,7 @@
 // onto its running sum, and at the last pass divides, gamma-corrects and quantises
 // (tracer.rs:170-184). Launched by render.hip through launch_sum (sum.h).
 #include "sum.h"
+#include "trace_kernel.h"  // slot_xy (with rt_core.h): the trace kernel's pixel-slot order
 
 namespace fr {
 

@@ -1,5 +1,5 @@
 """Host check of the invariant-divisor division the trace kernel uses to split a work
-item into (sample block, pixel slot): render.hip `fastdiv` / `fastdiv_magic`
+item into (sample block, pixel slot): kparams.h `fastdiv` / `fastdiv_magic`
 (Granlund-Montgomery, 32-bit, round-up magic with the add-and-shift fix-up). The kernel
 divides the tile-block index (< 2^26) by n_tiles (1 .. 2^16); this restates the formula
 in numpy u64 arithmetic and compares it with exact integer division."""

@@ -17,11 +17,11 @@ from oracle import scene_ref as S
 from tests.golden import make_golden as G
 from tests.test_gpu_parity import GOLDEN, _product_scene, assert_parity, random_scene
 
-JIT_MAX = 64  # jit.h kJitMaxPrims
+JIT_MAX = 64  # plan.h kJitMaxPrims
 
 
 def _box_records(prims):
-    """64-B device records (render.hip upload_scene) of axis-aligned boxes."""
+    """64-B device records (pack.cpp pack_scene) of axis-aligned boxes."""
     words = []
     for p in prims:
         g = list(p.g[:6]) if hasattr(p, "g") else p

@@ -22,19 +22,26 @@ mkdir -p "$root/fo-rma_amd/build/ab"
 # embed REV's trace_kernel.h (and what it includes), so the A/B covers the hiprtc kernel too
 c="$tmp/fo-rma_amd/csrc"
 mkdir -p "$tmp/fo-rma_amd/build"
-python3 "$c/embed_sources.py" "$tmp/fo-rma_amd/build/jit_sources.inc" trace_kernel.h="$c/trace_kernel.h" \
+kparams=""
+[ -f "$c/kparams.h" ] && kparams="kparams.h=$c/kparams.h"  # the launch contract's own header (once split out)
+python3 "$c/embed_sources.py" "$tmp/fo-rma_amd/build/jit_sources.inc" trace_kernel.h="$c/trace_kernel.h" $kparams \
   rt_core.h="$c/rt_core.h" bvh.h="$c/bvh.h" forma_rt.h="$tmp/include/forma_rt.h"
-g++ -O2 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -Wall -Wno-unused-function $defs -D__HIP_PLATFORM_AMD__ \
-  -I/opt/rocm/include -c "$c/jit.cpp" -o "$tmp/jit.o"
+HOST="g++ -O2 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -Wall -Wno-unused-function $defs"
+$HOST -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -c "$c/jit.cpp" -o "$tmp/jit.o"
 FP="-ffp-contract=off -fno-fast-math -fhip-fp32-correctly-rounded-divide-sqrt -fno-gpu-flush-denormals-to-zero"
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC $FP -fno-slp-vectorize $defs \
-  -c "$tmp/fo-rma_amd/csrc/render.hip" -o "$tmp/render.o"
-objs="$tmp/render.o"
-if [ -f "$tmp/fo-rma_amd/csrc/sum.hip" ]; then  # sum_kernel's own unit (round 4 on)
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC $FP -fno-slp-vectorize $defs \
-    -c "$tmp/fo-rma_amd/csrc/sum.hip" -o "$tmp/sum.o"
-  objs="$objs $tmp/sum.o"
-fi
+objs=""
+# render.hip, and the units split from it where REV has them: sum_kernel (round 4 on), the
+# diagnostics kernels, the frame plan, the scene packer and the multi-device context
+for u in render sum selftest; do
+  [ -f "$c/$u.hip" ] || continue
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC $FP -fno-slp-vectorize $defs -c "$c/$u.hip" -o "$tmp/$u.o"
+  objs="$objs $tmp/$u.o"
+done
+for u in plan pack mctx; do
+  [ -f "$c/$u.cpp" ] || continue
+  $HOST -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -c "$c/$u.cpp" -o "$tmp/$u.o"
+  objs="$objs $tmp/$u.o"
+done
 b="$root/fo-rma_amd/build"
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o "$b/ab/libforma_rt_$name.so" $objs \
   "$b/scene.o" "$b/json_min.o" "$b/bvh.o" "$b/post.o" "$b/jit_cache.o" "$tmp/jit.o" -L/opt/rocm/lib -lhiprtc -Wl,-rpath,/opt/rocm/lib

@@ -41,7 +41,7 @@ OPTS = ["-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fhip-fp32-
 
 
 def scene_records(name="scene_08"):
-    """The scene's 64-B device records as render.hip upload_scene lays them out (spheres,
+    """The scene's 64-B device records as pack.cpp pack_scene lays them out (spheres,
     boxes and planes; the kind in g3.w)."""
     sys.path.insert(0, os.path.join(ROOT, "fo-rma_amd"))
     import forma_rt as fr
