@@ -9,8 +9,7 @@
 // list-order loop (tracer.rs:195-200) because every primitive's candidate t does not
 // depend on t_max and exact ties are broken by list index (render.hip, the BVH hit
 // loop), whatever order the leaves are visited in.
-#ifndef FR_BVH_H
-#define FR_BVH_H
+#pragma once
 
 #include <stdint.h>
 
@@ -94,5 +93,3 @@ uint32_t bvh_max_depth(const std::vector<BvhSegment>& segs, const std::vector<Bv
 #endif
 
 }  // namespace fr
-
-#endif

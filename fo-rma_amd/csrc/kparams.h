@@ -1,11 +1,12 @@
 // kparams.h — the launch contract the host driver and the device code share: block and
-// tile sizes, the KParams flag bits, the sample-buffer and LDS layout constants, the
-// kernel-selection tuning values, KParams itself and the invariant division it carries.
+// tile sizes, the KParams flag bits, the sample-buffer and LDS layout constants, KParams
+// itself and the invariant division it carries. The FR_* tuning values: tuning.h.
 //
 // Host-safe: compiles under g++ with no HIP headers (plan.cpp, pack.cpp), under hipcc
 // (trace_kernel.h, sum.h) and under hiprtc (the run-time build of trace_kernel.h).
 #pragma once
 #include <stdint.h>
+#include "tuning.h"
 
 #if defined(__HIPCC_RTC__) || defined(__HIPCC__) || defined(__HIP__)
 #define FR_KHD __host__ __device__ __forceinline__
@@ -21,23 +22,6 @@ constexpr uint32_t kBlock = 256;      // 4 waves, one 8x8 pixel tile each
 constexpr uint32_t kStripRows = 8;    // rows per shard strip == tile height
 constexpr uint32_t kMaxDepth = 64;    // LDS stack bound (64 KB per workgroup)
 constexpr uint32_t kMaxWgPerCu = 8;   // 2048 threads per CU / kBlock: the persistent grid's cap
-#ifndef FR_KREJ
-#define FR_KREJ 4  // rejection loop: lanes left to the next iteration (tuning only, results unchanged)
-#endif
-// ... for the 8-B-record kernels (scenes of <= 15 primitives, the headline's): measured
-// C3 trace 20.81 -> 20.69 ms at 6 (7 and 8 the same within noise); 6 on the other kernels
-// cost C2 +1.7 % and a 10k-sphere BVH frame +1.2 %, so they keep FR_KREJ
-// Re-tuned for the scene-specialised kernel (round 3): 9 with
-// FR_CLAIM_MIN_NIB 3 streams C3 at 16.49 ms per frame against 16.63 (6 / 2), three runs;
-// shard 0/8 unchanged (tools/gpu_knob_shards.sh, profiles/r03k_knob_shards.log)
-#ifndef FR_KREJ_NIB
-#define FR_KREJ_NIB 9
-#endif
-// ... for the BVH kernels with 8-B attenuation-class records: C5 trace 39.51 -> 39.17 ms at 2
-// (0: 39.87, 1: 39.27, 3: 39.31, 6: 40.14; profiles/r06af_ab_c5_krej.log, four runs)
-#ifndef FR_KREJ_BVH
-#define FR_KREJ_BVH 2
-#endif
 constexpr uint32_t kSmallDepth = 8;
 // Deferred unwind (DEFER kernels: depth <= 8, <= kDeferMaxPrims primitives, no BVH, not
 // render_mt): a path's sample slot holds the record {t, winners 0-3, winners 4-7} instead
@@ -58,28 +42,14 @@ constexpr uint32_t kNibbleMaxPrims = 15;
 constexpr uint32_t kNibbleUnit = 15;
 constexpr uint32_t KF_NIBBLE = 1u << 29;           // internal: 8-B deferred records
 constexpr uint32_t KF_DIFFUSE = 1u << 28;          // internal: no metal/dielectric (trace_kernel MAT = 1)
-// FR_SKY_DEFER builds (A/B): the 8-B-record kernel stores 12-B records {d.y, dot(d, d),
-// winners} and sum_kernel computes the sky parameter, at full SIMD width, instead of the
-// trace kernel in the few lanes whose path escapes in a given iteration. dot(d, d) = -1
-// (which no sum of squares is) marks an absorbed path.
-#ifdef FR_SKY_DEFER
-constexpr bool kSkyDefer = true;
-#else
-constexpr bool kSkyDefer = false;
-#endif
-#ifndef FR_BLOCK_SAMPLES
-#define FR_BLOCK_SAMPLES 16  // RNG contract: one stream per 16-sample block (oracle.cpp agrees)
-#endif
-constexpr uint32_t kBlockSamples = FR_BLOCK_SAMPLES;  // samples per RNG stream (numerics contract)
+// RNG contract, not tuning: one stream per 16-sample block (oracle.cpp agrees; the goldens pin it)
+constexpr uint32_t kBlockSamples = 16;  // samples per RNG stream (numerics contract)
 // The last block of a pixel with more than one block is split into sub-blocks of
 // kFineSamples samples, each its own stream (key kFineKey | s / kFineSamples): the queue
 // ends with short items, so the drain after the last claim is short.
 // (Splitting the last 2, 3 or 4 blocks measured 0.9-2.7 % slower at 1 GPU for 1-2 % at
 // shard 0 of 8; one queue head per XCD, with stealing, 1.4 % slower.)
-#ifndef FR_FINE_SAMPLES
-#define FR_FINE_SAMPLES 4
-#endif
-constexpr uint32_t kFineSamples = FR_FINE_SAMPLES;
+constexpr uint32_t kFineSamples = 4;
 constexpr uint32_t kFineSub = kBlockSamples / kFineSamples;  // sub-blocks per block
 constexpr uint32_t kFineKey = 0x80000000u;
 static_assert(kFineSamples >= 1 && kBlockSamples % kFineSamples == 0 && kFineSub <= 4,
@@ -138,24 +108,16 @@ constexpr uint32_t kRecLds = 64;    // whole 64-B records staged in LDS for smal
 // Sample colours a lane stages in LDS before storing them to the (item-major) sample
 // buffer: 4 x 12 B = three 16-B stores per 4 samples (4 x 8 B = two, for 8-B records)
 // instead of four scattered stores, which L2 wrote back as partial lines (3.5x WRITE_SIZE).
-// The BVH kernels stage 2 samples when their LDS allows (below).
-#ifndef FR_STAGE
-#define FR_STAGE 4  // 1 or 4 (A/B builds)
-#endif
 // The BVH kernels stage 2 samples when the 6 KB this adds to their LDS (which holds the
 // traversal stack) keeps their resident workgroups per CU (KF_STAGE, decided at launch):
 // C5 66.8 -> 64.3 ms; on scenes whose LDS tables fill the CU it would cost a workgroup.
-#ifndef FR_BVH_STAGE
-#define FR_BVH_STAGE 2
-#endif
 // (BVH kernels with 8-B records stage like the list kernels: their LDS holds no unwind stack)
-FR_KHD_CONSTEXPR uint32_t stage_samples(bool bvh, bool nib = false) {
-  return bvh && !nib ? FR_BVH_STAGE : FR_STAGE;
-}
-// FR_BVH_RSTAGE=1: the BVH kernels hold a pair's first colour in registers instead of LDS
-// (3 VGPRs, none of the traversal stack's LDS), so every BVH launch stores whole pairs.
-#ifndef FR_BVH_RSTAGE
-#define FR_BVH_RSTAGE 0
-#endif
+constexpr uint32_t kStage = 4, kBvhStage = 2;
+FR_KHD_CONSTEXPR uint32_t stage_samples(bool bvh, bool nib = false) { return bvh && !nib ? kBvhStage : kStage; }
+// a sub-block's group store starts at the sub-block's first sample and never writes
+// another sub-block's slots
+static_assert(kStage <= kFineSamples && kBvhStage <= kFineSamples && kFineSamples % kStage == 0 &&
+                  kFineSamples % kBvhStage == 0,
+              "a staging group never exceeds a sub-block");
 
 }  // namespace fr

@@ -124,8 +124,7 @@ int make_plan(const fr_params& p, float cam_reach, const SceneFacts& sf, int num
   if (fp.defer) kp.flags |= KF_DEFER;
   if (fp.nibble) kp.flags |= KF_NIBBLE;
   if (fp.diffuse_k) kp.flags |= KF_DIFFUSE;
-  fp.wps = fp.nibble && !kSkyDefer ? 2u : 3u;
-  fp.sum_kind = fp.wps == 3 && kSkyDefer && fp.nibble ? 1 : 0;
+  fp.wps = fp.nibble ? 2u : 3u;
   fp.per_block = static_cast<size_t>(kp.P) * kp.ks * fp.wps * sizeof(float);
   // Passes of nb_pass blocks each. With more than one pass the sample buffer holds two
   // pass slots (a pass traces into one while the previous pass's sum reads the other).
@@ -192,8 +191,7 @@ int make_plan(const fr_params& p, float cam_reach, const SceneFacts& sf, int num
   fp.lds = (stage_n > 1 && (!fp.use_bvh || fp.nibble) ? kBlock * stage_n * fp.wps * sizeof(float) : 0u) +
            (n_att ? n_att + 1 : 0) * 16 + n_rec * 64 + stack_bytes +
            (fp.use_bvh ? (sf.bvh_levels + 1u) * kBlock * sizeof(uint32_t) : 0u);  // + the sentinel row
-  fp.stage_bytes =
-      fp.use_bvh && !fp.nibble && stage_n > 1 && !FR_BVH_RSTAGE ? kBlock * stage_n * 3 * sizeof(float) : 0u;
+  fp.stage_bytes = fp.use_bvh && !fp.nibble && stage_n > 1 ? kBlock * stage_n * 3 * sizeof(float) : 0u;
   // the scene-specialised kernel (jit.h): list-loop scenes of <= kJitMaxPrims primitives,
   // when the caller asks (FR_FLAG_SCENE_JIT; FR_SCENE_JIT=1 / 0 forces it on / off)
   const bool want = env.scene_jit >= 0 ? env.scene_jit != 0 : (p.flags & FR_FLAG_SCENE_JIT) != 0;
@@ -237,6 +235,21 @@ std::string kernel_name(const int t[8]) {
   snprintf(name, sizeof name, "fr::trace_kernel<%d, %s, %d, %d, %s, %s, %d, %d>", t[0], b(t[1]), t[2], t[3], b(t[4]),
            b(t[5]), t[6], t[7]);
   return name;
+}
+
+std::string tuning_defines() {
+  std::string d;
+  auto def = [&](const char* name, long v) { d += std::string("#define ") + name + " " + std::to_string(v) + "\n"; };
+#define X(n) def(#n, n);
+  FR_TUNING(X)
+#undef X
+#ifdef FR_PROF
+  d += "#define FR_PROF\n";  // section clocks go to the launch's counters, not device globals
+#endif
+#ifdef FR_SECCNT
+  d += "#define FR_SECCNT\n";  // region entry counts go to the launch's counters (tools/isa_sections.py)
+#endif
+  return d;
 }
 
 KernelId kernel_id(const KernelInputs& in) {

@@ -146,6 +146,9 @@ struct FramePlan {
   int slots = 1;
   size_t lds = 0;
   size_t stage_bytes = 0;  // BVH kernels: LDS for sample staging, taken if it costs no residency
+  // always 0 (the record's form follows KParams.flags) and read by nothing here. It stays for
+  // one reason: the previous revision's tests/c/plan_check.cpp prints it, and that revision's
+  // tests are run against this library before it is accepted. Delete it with the next change.
   int sum_kind = 0;
   bool jit_on = false, jit_wait = false, jit_cached_only = false;
   int bvh_stage = 0;     // PlanEnv's, for the grid sizing
@@ -230,5 +233,10 @@ struct KernelId {
 constexpr bool kTargBool[8] = {false, true, false, false, true, true, false, false};
 std::string kernel_name(const int targs[8]);  // "fr::trace_kernel<KS, HP, KREJ, MAXD, BV, MT, DEFER, MAT>"
 KernelId kernel_id(const KernelInputs& in);
+
+// This build's tuning values (tuning.h's FR_TUNING list) and instrument flags as #define
+// lines: the prelude of the run-time build of trace_kernel.h, which is then the same
+// specialisation as the one compiled into the library, with only the list walk replaced.
+std::string tuning_defines();
 
 }  // namespace fr

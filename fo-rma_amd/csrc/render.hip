@@ -33,18 +33,6 @@
 #include "sum.h"
 #include "trace_kernel.h"
 
-// The frame's setup (slot wait, counter clear, start events) goes on the stream its trace
-// runs on: with overlapping traces (stream2 every other frame) a setup on c->stream would
-// wait behind the previous frame's whole trace there, and so would this frame's trace.
-#ifndef FR_SETUP_ON_TRACE_STREAM
-#define FR_SETUP_ON_TRACE_STREAM 1
-#endif
-// a pipelined frame's queue head is cnt[31], cleared with its counters (before ev_start,
-// which stream2 waits for); passes of a multi-pass frame reuse two heads
-#ifndef FR_QUEUE_MEMSET
-#define FR_QUEUE_MEMSET 0
-#endif
-
 namespace fr {
 
 // ABI layout, mirrored by ctypes (forma_rt.py) and the Rust binding
@@ -239,63 +227,8 @@ static int grow_events(std::vector<hipEvent_t>& v, size_t n, unsigned flags) {
   return FR_OK;
 }
 
-// The host build's tuning and contract macros, so the run-time build of trace_kernel.h
-// is the same specialisation as the one compiled into the library, with only the list
-// walk replaced.
-static std::string jit_defines() {
-  std::string d;
-  auto def = [&](const char* name, long v) { d += std::string("#define ") + name + " " + std::to_string(v) + "\n"; };
-  def("FR_KREJ", FR_KREJ);
-  def("FR_KREJ_NIB", FR_KREJ_NIB);
-  def("FR_CLAIM_MIN", FR_CLAIM_MIN);
-  def("FR_CLAIM_MIN_NIB", FR_CLAIM_MIN_NIB);
-  def("FR_NUM_SGPR", FR_NUM_SGPR);
-  def("FR_BLOCK_SAMPLES", FR_BLOCK_SAMPLES);
-  def("FR_FINE_SAMPLES", FR_FINE_SAMPLES);
-  def("FR_STAGE", FR_STAGE);
-  def("FR_BVH_STAGE", FR_BVH_STAGE);
-  def("FR_STAGE_SMAJOR", FR_STAGE_SMAJOR);
-#ifdef FR_TRACE_PRIO
-  def("FR_TRACE_PRIO", FR_TRACE_PRIO);
-#endif
-#ifdef FR_SKY_DEFER
-  d += "#define FR_SKY_DEFER\n";
-#endif
-#ifdef FR_MIN_WAVES
-  def("FR_MIN_WAVES", FR_MIN_WAVES);
-#else
-  def("FR_NIB_WAVES", FR_NIB_WAVES);
-  def("FR_DIFF12_WAVES", FR_DIFF12_WAVES);
-#endif
-#ifdef FR_CAM_RESIDENT
-  d += "#define FR_CAM_RESIDENT\n";
-#endif
-#ifdef FR_SPHERE_IEEE
-  d += "#define FR_SPHERE_IEEE\n";
-#endif
-#ifdef FR_SKY_IEEE
-  d += "#define FR_SKY_IEEE\n";
-#endif
-#ifdef FR_DIV_2STEP
-  d += "#define FR_DIV_2STEP\n";
-#endif
-#ifdef FR_NO_UNROLL_NIB
-  d += "#define FR_NO_UNROLL_NIB\n";
-#endif
-#if FR_BOX_FMA
-  def("FR_BOX_FMA", FR_BOX_FMA);
-#endif
-#ifdef FR_PROF
-  d += "#define FR_PROF\n";  // section clocks go to the launch's counters, not device globals
-#endif
-#ifdef FR_SECCNT
-  d += "#define FR_SECCNT\n";  // region entry counts go to the launch's counters (tools/isa_sections.py)
-#endif
-  return d;
-}
-
 static JitSpec jit_spec(const KernelId& id, const uint32_t* rec, uint32_t n) {
-  return JitSpec{id.name.c_str(), id.targs, kTargBool, 8, jit_defines(), rec, n};
+  return JitSpec{id.name.c_str(), id.targs, kTargBool, 8, tuning_defines(), rec, n};
 }
 
 // The scene-specialised kernel of one render (jit.h), when the plan asks for one.
@@ -544,8 +477,11 @@ static int enqueue_frame(fr_ctx* c, const DeviceCopy* dc, const FramePlan& fp, K
                          int fs) {
   unsigned long long* const cnt = c->d_cnt + kCntWords * fs;
   c->t0 = std::chrono::steady_clock::now();
+  // The frame's setup (slot wait, counter clear, start events) goes on the stream its trace
+  // runs on: with overlapping traces (stream2 every other frame) a setup on c->stream would
+  // wait behind the previous frame's whole trace there, and so would this frame's trace.
   hipStream_t setup = c->stream;
-  if (FR_SETUP_ON_TRACE_STREAM && fp.fpipe && fp.fpipe_overlap && c->frame_parity) setup = c->stream2;
+  if (fp.fpipe && fp.fpipe_overlap && c->frame_parity) setup = c->stream2;
   // the last frame that used this slot's counters and samples (or, after a layout change,
   // every earlier frame) has been summed
   for (int k = 0; k < kFrameSlots; ++k)
@@ -593,7 +529,9 @@ static int enqueue_frame(fr_ctx* c, const DeviceCopy* dc, const FramePlan& fp, K
       args.kw.queue = reinterpret_cast<uint32_t*>(cnt + 31 - (fp.fpipe ? 0 : slot));
       args.kw.samples = samples;
       args.kw.wave_counters = wcnt;
-      if (!fp.fpipe || FR_QUEUE_MEMSET) HIPCHK(hipMemsetAsync(args.kw.queue, 0, sizeof(uint32_t), ts));
+      // a pipelined frame's queue head is cnt[31], cleared with its counters (before ev_start,
+      // which stream2 waits for); passes of a multi-pass frame reuse two heads
+      if (!fp.fpipe) HIPCHK(hipMemsetAsync(args.kw.queue, 0, sizeof(uint32_t), ts));
       HIPCHK(hipEventRecord(c->ev_trace[2 * traced], ts));
       if (c->log_on) HIPCHK(log_start(c, 0, ts));
       const Launched l = launch_trace(fp, c->num_cus, sk, ts, args);
@@ -614,7 +552,7 @@ static int enqueue_frame(fr_ctx* c, const DeviceCopy* dc, const FramePlan& fp, K
     }
     const int first = pass == 0, last = pass + 1 >= fp.passes;
     if (first && c->copy_pending) HIPCHK(hipStreamWaitEvent(c->stream_sum, c->ev_copy, 0));  // last gather done
-    HIPCHK(launch_sum(fp.wps, fp.sum_kind, sum_blocks ? sum_blocks : 1u, c->stream_sum, kp, samples, c->d_running,
+    HIPCHK(launch_sum(fp.wps, sum_blocks ? sum_blocks : 1u, c->stream_sum, kp, samples, c->d_running,
                       c->d_mean, c->d_u8, first, last, sum_att, sum_n));
     HIPCHK(hipEventRecord(c->ev_sum[pass], c->stream_sum));
     summed = pass + 1;

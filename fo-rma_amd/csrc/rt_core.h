@@ -99,11 +99,11 @@ FR_HD uint32_t rotl32(uint32_t x, int k) { return (x << k) | (x >> (32 - k)); }
 FR_HD uint32_t rng_next(Rng& r) {  // xoshiro128+ 1.0
   const uint32_t result = r.s0 + r.s3;
   const uint32_t t = r.s1 << 9;
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(FR_XOSHIRO_PLAIN)
+#if defined(__HIP_DEVICE_COMPILE__)
   // the same state transition with gfx950's three-input v_bitop3_b32 (0x96 = a ^ b ^ c):
   // s2' = s2 ^ s0 ^ t, s1' = s1 ^ (s2 ^ s0), s0' = s0 ^ (s3 ^ s1), s3' = rotl(s3 ^ s1, 11);
   // 6 VALU per draw instead of 7 (LLVM does not form bitop3 from xor chains); C3 trace
-  // 18.50 -> 18.15 ms, bit-identical (FR_XOSHIRO_PLAIN keeps the plain sequence for A/B)
+  // 18.50 -> 18.15 ms, bit-identical to the plain sequence (the host's, below)
   const uint32_t s3x = r.s3 ^ r.s1;
   const uint32_t s1n = __builtin_amdgcn_bitop3_b32(r.s1, r.s2, r.s0, 0x96);
   const uint32_t s2n = __builtin_amdgcn_bitop3_b32(r.s2, r.s0, t, 0x96);
@@ -146,7 +146,12 @@ constexpr float kSignedUnitScale = 1.1920928955078125e-07f;  // 2^-23
 constexpr float kUnitBallScaled = 70368744177664.0f;         // 2^46
 
 // utility.rs:4-13: p = 2*(r1, r2, 0) - (1, 1, 0), retry while dot(p,p) >= 1
-#ifndef FR_LENS_TRY
+// (trip-count hooks: trace_kernel.h's FR_DIAG builds define FR_DIAG_TRY and the counters
+// before this header; empty everywhere else)
+#ifdef FR_DIAG_TRY
+#define FR_LENS_TRY() FR_DIAG_TRY(g_fr_diag_lens)
+#define FR_RUS_TRY() FR_DIAG_TRY(g_fr_diag_rus)
+#else
 #define FR_LENS_TRY()
 #define FR_RUS_TRY()
 #endif
@@ -291,15 +296,10 @@ __device__ __forceinline__ bool recip_nr_ok(float x) {
 // scales to one in [1, 2) x [1, 2) by powers of two that scale both results exactly: all
 // 2^46 such pairs are checked on the device (fr_selftest_div,
 // tests/test_gpu_parity.py::test_div_rn_exhaustive). Used only where the operand ranges
-// hold by construction. FR_DIV_2STEP: the second correction as well (the round-4 form).
+// hold by construction.
 __device__ __forceinline__ float div_rn(float a, float b, float y) {
   const float q0 = a * y;
-  const float q1 = __builtin_fmaf(__builtin_fmaf(-b, q0, a), y, q0);
-#ifdef FR_DIV_2STEP
-  return __builtin_fmaf(__builtin_fmaf(-b, q1, a), y, q1);
-#else
-  return q1;
-#endif
+  return __builtin_fmaf(__builtin_fmaf(-b, q0, a), y, q0);
 }
 #endif
 
@@ -439,10 +439,7 @@ FR_HD Slab slab3_fused(V3 lo, V3 hi, V3 oinv, V3 inv) {
 // (lo - o) * inv, and one instruction per distinct slab coordinate of the scene kernel (o inv
 // is per segment): C3 14.84 -> 14.48 ms per streamed frame (profiles/r06e_ab_boxfma.log).
 // The clamp keeps zero and tiny direction components finite (inf * lo - inf * o would be
-// NaN). FR_BOX_FMA=0 builds the round-5 form (A/B; the oracle's OR_BOX_FMA=0 matches it).
-#ifndef FR_BOX_FMA
-#define FR_BOX_FMA 1
-#endif
+// NaN). The oriented box keeps its own (lo - o) * inv form (slab3).
 constexpr float kBoxInvClamp = 0x1p100f;
 FR_HD float box_inv_clamp(float inv) { return fmin_num(fmax_num(inv, -kBoxInvClamp), kBoxInvClamp); }
 // recip_nr's range narrowed to |x| >= 2^-100: there RN(1 / x) is within the clamp
@@ -451,9 +448,8 @@ FR_HD bool recip_box_ok(float x) {
   return (ax >= 0x1p-100f) & (ax < 0x1p126f);
 }
 FR_HD Slab slab3_box(V3 lo, V3 hi, V3 o, V3 inv, V3 oinv) {
-  if (FR_BOX_FMA) return slab3_fused(lo, hi, oinv, inv);
-  (void)oinv;
-  return slab3(lo, hi, o, inv);
+  (void)o;  // (slab3's signature; o enters through oinv)
+  return slab3_fused(lo, hi, oinv, inv);
 }
 
 // Root selection: returns true and the accepted t if the box is hit in (t_min, t_max).

@@ -6,14 +6,7 @@
 
 namespace fr {
 
-#ifndef FR_SUM_UNROLL
-#define FR_SUM_UNROLL 2
-#endif
-constexpr int kSumUnroll = FR_SUM_UNROLL;
-#ifndef FR_SUM_UNROLL_SKYD
-#define FR_SUM_UNROLL_SKYD 1
-#endif
-constexpr int kSumUnrollSkyd = FR_SUM_UNROLL_SKYD;
+constexpr int kSumUnroll = FR_SUM_UNROLL;  // tuning.h
 static_assert(kSumThreads % 64u == 0 && kSumThreads <= kDeferUnit + 1u, "whole waves, one table pass or more");
 
 // Adds each pixel's sample colours of this pass, in sample order, onto its running
@@ -27,24 +20,16 @@ static_assert(kSumThreads % 64u == 0 && kSumThreads <= kDeferUnit + 1u, "whole w
 // here from a 12-B-per-entry attenuation table (tile + table fit three workgroups per CU).
 // WPS = 2: 8-B records {t, 4-bit winners} (KF_NIBBLE).
 
-// FR_SUM_VGPR_CAP: the sum runs beside seven trace workgroups per CU,
-// whose 56 VGPRs per wave leave 120 per SIMD lane for one sum wave
-#ifndef FR_SUM_VGPRS
-#define FR_SUM_VGPRS 120
-#endif
-#if FR_SUM_VGPRS
-#define FR_SUM_VGPR_CAP __attribute__((amdgpu_num_vgpr(FR_SUM_VGPRS)))
-#else
-#define FR_SUM_VGPR_CAP
-#endif
-// KIND 1: FR_SKY_DEFER's 12-B records only (a kernel without the other paths' registers)
-template <uint32_t WPS, int KIND = 0>
+// The VGPR cap of both sum kernels: the sum runs beside seven trace workgroups per CU,
+// whose 56 VGPRs per wave leave 512 - 7 x 56 = 120 per SIMD lane for one sum wave
+constexpr int kSumVgprs = 120;
+#define FR_SUM_VGPR_CAP __attribute__((amdgpu_num_vgpr(kSumVgprs)))
+template <uint32_t WPS>
 __global__ __launch_bounds__(kSumThreads) FR_SUM_VGPR_CAP void sum_kernel(KParams kp, const float* __restrict__ samples,
                                                           float* __restrict__ running, float* __restrict__ out_mean,
                                                           uint8_t* __restrict__ out_u8, int first, int last,
                                                           const float4* __restrict__ att, uint32_t n_prims) {
   constexpr uint32_t kSumSlot = WPS * kBlockSamples + 1;  // floats per slot in LDS (odd stride)
-  constexpr int kUnroll = KIND == 1 ? kSumUnrollSkyd : kSumUnroll;
   // one LDS block, the attenuation table first: its entries then sit at LDS byte offset
   // 12 x index, and the per-level reads need no base-address add (the table behind the
   // tile, at 33,792 B, cost a v_or per level: 8 of ~60 VALU per sample)
@@ -55,17 +40,10 @@ __global__ __launch_bounds__(kSumThreads) FR_SUM_VGPR_CAP void sum_kernel(KParam
   float4* const att16 = reinterpret_cast<float4*>(lds_sum);
   float* const att_s = lds_sum + 4 * 16;  // KF_DEFER: attenuation rgb, entry kDeferUnit = 1
   float* const tile = lds_sum + kTable;
-#ifndef FR_SUM_PRIO
-#define FR_SUM_PRIO 0
-#endif
   // Pipelined frames run this kernel on the CU slot the next frame's
   // trace leaves free, where it takes about as long as the trace. A raised wave priority
-  // slowed the trace by more than it sped the sum (FR_SUM_PRIO=3: C3 streamed 16.65 ->
+  // slowed the trace by more than it sped the sum (s_setprio 3: C3 streamed 16.65 ->
   // 17.07 ms per frame in round 3; 1: 16.26 -> 16.73 in round 4): not used.
-  if (FR_SUM_PRIO) __builtin_amdgcn_s_setprio(FR_SUM_PRIO);
-#ifdef FR_SUM_STUB
-  return;  // measurement-only builds (tools/stream_ab.py --allow-diff): the frame without its sum
-#endif
   const uint32_t t = threadIdx.x;
   const bool defer = (kp.flags & KF_DEFER) != 0;
   if (defer) {  // the kDeferUnit + 1 table entries, kSumThreads at a time
@@ -84,16 +62,10 @@ __global__ __launch_bounds__(kSumThreads) FR_SUM_VGPR_CAP void sum_kernel(KParam
   const bool mt = (kp.flags & FR_FLAG_MT_BANDS) != 0;
   const bool mt_zero = mt && !(kp.band_h && y / kp.band_h < 4u);  // rows render_mt never fills stay 0
   V3 sum = (first || !valid) ? V3{0.0f, 0.0f, 0.0f} : V3{running[3 * q], running[3 * q + 1], running[3 * q + 2]};
-#ifndef FR_SUM_BUFLOAD
-#define FR_SUM_BUFLOAD 1
-#endif
-#ifndef FR_SUM_WAITFIX
-#define FR_SUM_WAITFIX 1
-#endif
   // The running sum's loads land here, before the first block's loads are issued. Left to
   // the compiler, the wait for them sat on the first add of every block's sample loop,
   // where (global loads complete in order) it also waited for the next block's prefetch.
-  if (FR_SUM_WAITFIX) asm volatile("" : "+v"(sum.x), "+v"(sum.y), "+v"(sum.z));
+  asm volatile("" : "+v"(sum.x), "+v"(sum.y), "+v"(sum.z));
   const float fspp = static_cast<float>(kp.spp);
   const uint32_t per = WPS * kp.ks;  // floats per slot in the buffer
   // full 16-sample slots: block bl + 1's loads are issued before block bl is summed, so
@@ -105,32 +77,17 @@ __global__ __launch_bounds__(kSumThreads) FR_SUM_VGPR_CAP void sum_kernel(KParam
   auto load_block = [&](uint32_t bl) {
     // 192-B (128-B) slots: 16-B aligned
     const float4* src4 = reinterpret_cast<const float4*>(samples + WPS * (static_cast<size_t>(bl * kp.P + q0) * kp.ks));
-    if (FR_SUM_BUFLOAD) {
-      // buffer loads: a 32-bit lane offset per load instead of a 64-bit address; the
-      // descriptor's range (the workgroup's n4 float4) returns 0 past the last slot. The
-      // whole offset is in the lane operand: the raw-buffer range check covers the lane
-      // offset, and the scalar offset may be outside it on this family
-      const __amdgpu_buffer_rsrc_t r =
-          __builtin_amdgcn_make_buffer_rsrc(const_cast<float4*>(src4), 0, static_cast<int>(n4 * 16u), 0x00020000);
-      typedef float v4f __attribute__((ext_vector_type(4)));
-#pragma unroll
-      for (uint32_t k = 0; k < kV; ++k) {
-        const v4f x = __builtin_amdgcn_raw_buffer_load_b128(r, t * 16u + k * kSumThreads * 16u, 0, 0);
-        v[k] = make_float4(x.x, x.y, x.z, x.w);
-      }
-      return;
-    }
+    // buffer loads: a 32-bit lane offset per load instead of a 64-bit address; the
+    // descriptor's range (the workgroup's n4 float4) returns 0 past the last slot. The
+    // whole offset is in the lane operand: the raw-buffer range check covers the lane
+    // offset, and the scalar offset may be outside it on this family
+    const __amdgpu_buffer_rsrc_t r =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<float4*>(src4), 0, static_cast<int>(n4 * 16u), 0x00020000);
+    typedef float v4f __attribute__((ext_vector_type(4)));
 #pragma unroll
     for (uint32_t k = 0; k < kV; ++k) {
-      const uint32_t i = t + k * kSumThreads;
-      if (FR_SUM_WAITFIX) {
-        // every lane loads (past the last slot: the last float4 again), so the loads and
-        // the tile stores below are straight-line code: the wait before each store is for
-        // its own load, and no load waits for the one before it
-        v[k] = src4[min(i, n4 - 1u)];
-      } else if (i < n4) {
-        v[k] = src4[i];
-      }
+      const v4f x = __builtin_amdgcn_raw_buffer_load_b128(r, t * 16u + k * kSumThreads * 16u, 0, 0);
+      v[k] = make_float4(x.x, x.y, x.z, x.w);
     }
   };
   if (kp.ks == kBlockSamples && kp.nb) load_block(0);
@@ -140,15 +97,16 @@ __global__ __launch_bounds__(kSumThreads) FR_SUM_VGPR_CAP void sum_kernel(KParam
     if (kp.ks == kBlockSamples) {
 #pragma unroll
       for (uint32_t k = 0; k < kV; ++k) {
+        // every lane stores (slots past nq hold the loads' zeros and are never read), so the
+        // loads and these stores are straight-line code: the wait before each store is for
+        // its own load
         const uint32_t i = t + k * kSumThreads;
-        if (FR_SUM_WAITFIX || i < n4) {  // (slots past nq are never read)
-          const uint32_t slot = i / kV, w = (i - slot * kV) * 4u;
-          float* d = tile + slot * kSumSlot + w;
-          d[0] = v[k].x;
-          d[1] = v[k].y;
-          d[2] = v[k].z;
-          d[3] = v[k].w;
-        }
+        const uint32_t slot = i / kV, w = (i - slot * kV) * 4u;
+        float* d = tile + slot * kSumSlot + w;
+        d[0] = v[k].x;
+        d[1] = v[k].y;
+        d[2] = v[k].z;
+        d[3] = v[k].w;
       }
       if (bl + 1u < kp.nb) load_block(bl + 1u);
     } else {
@@ -159,9 +117,9 @@ __global__ __launch_bounds__(kSumThreads) FR_SUM_VGPR_CAP void sum_kernel(KParam
       const uint32_t n = min(kBlockSamples, kp.spp - (kp.b0 + bl) * kBlockSamples);
       const float* c = tile + t * kSumSlot;
       // FR_SUM_UNROLL: samples whose colour rebuilds interleave (the sums stay in order)
-#pragma unroll kUnroll
+#pragma unroll kSumUnroll
       for (uint32_t j = 0; j < n; ++j, c += WPS) {
-        if (WPS == 2 && KIND == 0) {
+        if (WPS == 2) {
           // 8-B record: terminal, then a_7 ... a_0 from 4-bit entries (kNibbleUnit: 1)
           const uint32_t tb = __float_as_uint(c[0]), w = __float_as_uint(c[1]);
           V3 col = tb == kDeferAbsorbed ? V3{0.0f, 0.0f, 0.0f} : sky_from_t(c[0]);
@@ -175,25 +133,7 @@ __global__ __launch_bounds__(kSumThreads) FR_SUM_VGPR_CAP void sum_kernel(KParam
             col = mul(V3{e.x, e.y, e.z}, col);
           }
           sum = add(sum, col);
-        } else if (KIND == 1 || (kSkyDefer && (kp.flags & KF_NIBBLE))) {
-          // FR_SKY_DEFER's 12-B record {d.y, dot(d, d), winners}: the sky parameter here
-          const float dd = c[1];
-          const uint32_t w = __float_as_uint(c[2]);
-#ifdef FR_SKY_SUM_IEEE
-          const float tt = sky_t_from(c[0], dd);
-#else
-          const float tt = sky_t_fast_from(c[0], dd);  // bit-identical (fr_selftest_ops op 14)
-#endif
-          V3 col = __float_as_uint(dd) == kDeferAbsorbed ? V3{0.0f, 0.0f, 0.0f} : sky_from_t(tt);
-          const uint32_t w4 = w << 4;
-#pragma unroll
-          for (int k = 7; k >= 0; --k) {
-            const uint32_t off = (((k & 1) ? w : w4) >> (8 * (k >> 1))) & 0xF0u;
-            const float4 e = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(att16) + off);
-            col = mul(V3{e.x, e.y, e.z}, col);
-          }
-          sum = add(sum, col);
-        } else if (KIND == 0 && defer) {
+        } else if (defer) {
           // the deferred unwind (kDeferUnit): terminal, then a_7 ... a_0 innermost first
           const uint32_t tb = __float_as_uint(c[0]), lo = __float_as_uint(c[1]), hi = __float_as_uint(c[2]);
           V3 col = tb == kDeferAbsorbed ? V3{0.0f, 0.0f, 0.0f} : sky_from_t(c[0]);
@@ -203,10 +143,10 @@ __global__ __launch_bounds__(kSumThreads) FR_SUM_VGPR_CAP void sum_kernel(KParam
             col = mul(V3{e[0], e[1], e[2]}, col);
           }
           sum = add(sum, col);
-        } else if (KIND == 0 && mt) {  // save_image_mt (tracer.rs:140-145): acc += (sqrt(c) * 255) as u8 / sample
+        } else if (mt) {  // save_image_mt (tracer.rs:140-145): acc += (sqrt(c) * 255) as u8 / sample
           sum = add(sum, V3{static_cast<float>(to_u8(c[0])) / fspp, static_cast<float>(to_u8(c[1])) / fspp,
                             static_cast<float>(to_u8(c[2])) / fspp});
-        } else if (KIND == 0) {
+        } else {
           sum = add(sum, V3{c[0], c[1], c[2]});
         }
       }
@@ -255,10 +195,7 @@ __global__ __launch_bounds__(kSumThreads) FR_SUM_VGPR_CAP void sum_kernel(KParam
 // slots, 8 KB) into registers, the next block's slot while this one is summed. Beside the
 // next frame's trace this kernel runs one wave per SIMD: the tile's 64 LDS writes and reads
 // per thread and block, and its two barriers per block, were what it waited on there.
-// Same sums in the same order as sum_kernel<2, 0> (FR_SUM_DIRECT=0 selects that one).
-#ifndef FR_SUM_DIRECT
-#define FR_SUM_DIRECT 1
-#endif
+// Same sums in the same order as sum_kernel<2>, which takes the other 8-B-record launches.
 __global__ __launch_bounds__(kSumThreads) FR_SUM_VGPR_CAP void sum_nib_kernel(
     KParams kp, const float* __restrict__ samples, float* __restrict__ running, float* __restrict__ out_mean,
     uint8_t* __restrict__ out_u8, int first, int last, const float4* __restrict__ att, uint32_t n_prims) {
@@ -337,21 +274,18 @@ __global__ __launch_bounds__(kSumThreads) FR_SUM_VGPR_CAP void sum_nib_kernel(
   }
 }
 
-hipError_t launch_sum(uint32_t wps, int kind, uint32_t blocks, hipStream_t stream, const KParams& kp,
+hipError_t launch_sum(uint32_t wps, uint32_t blocks, hipStream_t stream, const KParams& kp,
                       const float* samples, float* running, float* out_mean, uint8_t* out_u8, int first, int last,
                       const float4* att, uint32_t n_prims) {
   const dim3 grid(blocks), block(kSumThreads);
-  if (wps == 2 && FR_SUM_DIRECT && kp.ks == kBlockSamples && !(kp.flags & FR_FLAG_MT_BANDS))
+  if (wps == 2 && kp.ks == kBlockSamples && !(kp.flags & FR_FLAG_MT_BANDS))
     hipLaunchKernelGGL(sum_nib_kernel, grid, block, 0, stream, kp, samples, running, out_mean, out_u8, first, last,
                        att, n_prims);
   else if (wps == 2)
-    hipLaunchKernelGGL((sum_kernel<2, 0>), grid, block, 0, stream, kp, samples, running, out_mean, out_u8, first,
-                       last, att, n_prims);
-  else if (kind == 1)
-    hipLaunchKernelGGL((sum_kernel<3, 1>), grid, block, 0, stream, kp, samples, running, out_mean, out_u8, first,
+    hipLaunchKernelGGL((sum_kernel<2>), grid, block, 0, stream, kp, samples, running, out_mean, out_u8, first,
                        last, att, n_prims);
   else
-    hipLaunchKernelGGL((sum_kernel<3, 0>), grid, block, 0, stream, kp, samples, running, out_mean, out_u8, first,
+    hipLaunchKernelGGL((sum_kernel<3>), grid, block, 0, stream, kp, samples, running, out_mean, out_u8, first,
                        last, att, n_prims);
   return hipGetLastError();
 }

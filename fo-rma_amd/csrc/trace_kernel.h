@@ -43,29 +43,13 @@ __device__ unsigned int g_fr_tb_cost[1u << 20];
 __device__ unsigned int g_fr_wave_iters[2 * 65536];
 // every 64th wave: the time of each of its first 1024 loop iterations (100 MHz)
 __device__ unsigned long long g_fr_iter_times[1024 * 1024];
-#define FR_LENS_TRY() FR_DIAG_TRY(g_fr_diag_lens)
-#define FR_RUS_TRY() FR_DIAG_TRY(g_fr_diag_rus)
 #endif
-#include "rt_core.h"
+#include "rt_core.h"  // (its rejection loops count their trips through FR_DIAG_TRY)
 #include "kparams.h"  // block sizes, KF_* bits, KParams, fastdiv: what the host driver shares
 
 namespace fr {
 
-// (FR_KREJ and its per-kernel values: kparams.h)
-#ifndef FR_CLAIM_MIN
-#define FR_CLAIM_MIN 1  // lanes that must wait for an item before the wave claims (tuning only)
-#endif
-// ... for the 8-B-record kernels (the headline's): C3 18.50 -> 18.28 ms at 2 (18.31 at 4, 18.46
-// at 6); 4 on every kernel cost C2 +2 %, so the others keep FR_CLAIM_MIN
-#ifndef FR_CLAIM_MIN_NIB
-#define FR_CLAIM_MIN_NIB 3
-#endif
-#ifndef FR_CLAIM_MIN_BVH
-#define FR_CLAIM_MIN_BVH FR_CLAIM_MIN
-#endif
-#ifndef FR_NUM_SGPR
-#define FR_NUM_SGPR 96
-#endif
+// (the FR_* tuning values: tuning.h)
 // work items reserved per step of the global counter: one tile of one sample block,
 // seeded by the wave's 64 lanes at once (trace_kernel's claim step)
 constexpr uint32_t kBatch = 64;
@@ -140,6 +124,22 @@ __device__ __forceinline__ RecRef rec_at(const float4* base, uint32_t i) {
   return RecRef{(cfloat*)(reinterpret_cast<uintptr_t>(base)) + 16u * i};
 }
 
+// The kernel's arguments read again from the kernarg segment (scalar loads), where they are
+// used, rather than held in SGPRs (and spilled) across the lane loop: the pointer passes
+// through an empty asm, so the compiler cannot hoist or merge the loads it feeds.
+// get(a) returns the wanted member of the arguments a by value.
+template <class Get>
+__device__ __forceinline__ auto kernarg_reload(const KArgs& args, Get get) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  typedef __attribute__((address_space(4))) const KArgs cargs;
+  cargs* ap = (cargs*)(__builtin_amdgcn_kernarg_segment_ptr());
+  asm volatile("" : "+s"(ap));
+  return get(*ap);
+#else
+  return get(args);  // (the host pass only parses the kernel)
+#endif
+}
+
 // Raw buffer loads (SGPR resource over a uniform base pointer). Used where an LDS and a
 // global read of the same value sit on two sides of a uniform branch: a buffer load
 // cannot be merged with the LDS read into one generic (flat) load.
@@ -152,24 +152,6 @@ __device__ __forceinline__ float4 buf_load4(const void* base, uint32_t byte_off)
 __device__ __forceinline__ uint32_t buf_load1(const void* base, uint32_t byte_off) {
   return __builtin_amdgcn_raw_buffer_load_b32(buf_rsrc(base), byte_off, 0, 0);
 }
-
-// FR_BVH_SCALAR_NODES=1: a node step whose walking lanes are all at one node reads it with
-// scalar loads (0, vector loads only: C5 trace 52.9 -> 62.3 ms, the vector memory path
-// returning 64 B per lane per step)
-#ifndef FR_STAGE_SMAJOR
-#define FR_STAGE_SMAJOR 0  // slot-major sample staging for 8-B records (A/B knob)
-#endif
-#ifndef FR_BVH_SCALAR_NODES
-#define FR_BVH_SCALAR_NODES 1
-#endif
-// FR_BVH_SCALAR_LEAVES=1: a leaf every lane is at is tested from scalar loads (A/B knob)
-#ifndef FR_BVH_SCALAR_LEAVES
-#define FR_BVH_SCALAR_LEAVES 1
-#endif
-// A staging group larger than a sub-block (FR_STAGE 8): a sub-block's group store starts at
-// the sub-block's first sample, so it never writes another sub-block's slots.
-static_assert(kFineSamples % FR_STAGE == 0 || FR_STAGE % kFineSamples == 0, "staging groups and sub-blocks nest");
-constexpr bool kStageSpansSub = FR_STAGE > kFineSamples;
 
 // FR_DIAG builds count, per phase, wave-level trips (one per SIMT pass of the wave)
 // and lane-level work, to measure SIMT efficiency. Never enabled in the product.
@@ -348,12 +330,6 @@ __device__ __forceinline__ void unroll_below(uint32_t n, F& f) {
 }
 
 #ifdef FR_JIT_N
-#ifndef FR_JIT_GROUP
-#define FR_JIT_GROUP 1024  // tests that may share terms (see the list walk; A/B knob)
-#endif
-#ifndef FR_JIT_PIN
-#define FR_JIT_PIN 1  // settle the winner after every test (see the list walk; A/B knob)
-#endif
 // The scene-specialised build's records: FR_JIT_REC (jit.cpp) lists each primitive's 64-B
 // device record as 16 u32 bit patterns (kind in word 15), so every float is exact,
 // signed zeros and non-finite values included.
@@ -370,7 +346,7 @@ struct JitRec {
 
 // amdgpu_num_sgpr caps the scalar registers (MI355X_MICROARCH.md "Residency and
 // cooperative launch": <= 80 SGPRs admit 8 workgroups of 256 threads per CU, 82-96
-// admit 7). Measured on scene_08: 96 beats 80 (fewer SGPR spills) and 102.
+// admit 7); FR_NUM_SGPR and its measurement: tuning.h.
 // MAT = 1: no metal or dielectric primitive (every scatter is lambertian: lambertian, light,
 // or none for stubs): the shading step drops those branches (the headline scene's case).
 template <int KS, bool HAS_PLANE, int KREJ, int MAXD, bool BVH, bool MT, int DEFER, int MAT = 0>
@@ -378,27 +354,12 @@ template <int KS, bool HAS_PLANE, int KREJ, int MAXD, bool BVH, bool MT, int DEF
 // BVH kernels at least 6 (<= 80); without the request the general (KS_ANY) and BVH
 // kernels settle at 83-94 VGPRs, 5 waves. Measured (tools/ab_bench.py): 7 for the list
 // kernels (scene_01 C2 37.9 -> 36.0 ms, a few VGPRs spilled to scratch), 6 for the BVH
-// ones (7 or 8 spill more: C5 +2-10 %, scene_06 +12-20 %). FR_MIN_WAVES=n forces n.
-#ifdef FR_MIN_WAVES
-#define FR_OCC_ATTR __attribute__((amdgpu_waves_per_eu(FR_MIN_WAVES)))
-#else
-#ifndef FR_NIB_WAVES
-// the 8-B-record (headline) kernel at 8 waves: with FR_KREJ_NIB = 6, C3 trace 20.67 ->
-// 20.49 ms and shard 0/4 -0.6 % (shard 0/8 +0.3 %); at KREJ 4 it had measured -0.3 % / +1.1 %
-#define FR_NIB_WAVES 8
-#endif
-#ifndef FR_DIFF12_WAVES
-#define FR_DIFF12_WAVES 7  // diffuse-only 12-B-record kernels (A/B knob)
-#endif
-#ifndef FR_BVH_WAVES
-// BVH kernels: 7 (72 VGPRs, one value spilled to scratch in the scatter step) over 6 (74
-// VGPRs with the split scalar/vector node step): C5 trace 54.0 -> 51.4 ms
-#define FR_BVH_WAVES 7
-#endif
+// ones (7 or 8 spill more: C5 +2-10 %, scene_06 +12-20 %). The per-kernel values and
+// FR_MIN_WAVES (n > 0 forces n on every kernel): tuning.h.
 #define FR_OCC_ATTR                                                                                      \
-  __attribute__((amdgpu_waves_per_eu(BVH ? FR_BVH_WAVES : DEFER == 2 ? FR_NIB_WAVES                   \
+  __attribute__((amdgpu_waves_per_eu(FR_MIN_WAVES ? FR_MIN_WAVES : BVH ? FR_BVH_WAVES                 \
+                                                      : DEFER == 2 ? FR_NIB_WAVES                       \
                                                       : (DEFER == 1 && MAT == 1) ? FR_DIFF12_WAVES : 7)))
-#endif
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(FR_NUM_SGPR))) FR_OCC_ATTR void trace_kernel(
     KArgs args) {
   // one by-value struct: the kernarg segment holds it at offset 0 (the camera is read
@@ -411,22 +372,13 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(FR_NUM_SGPR)
   // Entry n of the attenuations is (1, 1, 1): the depth-8 stack's empty levels hold n.
   // Staging the winner's data keeps per-lane global gathers off the shading path.
   // [STG > 1: kBlock x STG staged sample colours (12 B each), lane-major] in front.
-#ifndef FR_TRACE_PRIO
-#define FR_TRACE_PRIO 0
-#endif
-  // FR_TRACE_PRIO (A/B): the trace's waves issue ahead of a concurrently running sum_kernel
-  // (the frame pipeline), which then only takes the issue slots the trace
-  // leaves idle
-  if (FR_TRACE_PRIO) __builtin_amdgcn_s_setprio(FR_TRACE_PRIO);
   extern __shared__ uint32_t lds[];
   constexpr bool NIB = DEFER == 2;             // 8-B records, winners in a register
   constexpr uint32_t STG = stage_samples(BVH, NIB);
   constexpr bool DIFFUSE = MAT == 1;           // lambertian scatters only
-  constexpr bool SKYD = NIB && kSkyDefer;      // 12-B records {d.y, dot(d, d), winners}
-  constexpr uint32_t WPS = NIB && !SKYD ? 2u : 3u;  // words per sample in the buffer
+  constexpr uint32_t WPS = NIB ? 2u : 3u;      // words per sample in the buffer
   // list kernels always stage; BVH kernels when the launch gave them the LDS (KF_STAGE)
-  constexpr bool RSTG = BVH && FR_BVH_RSTAGE != 0;  // pairs staged in registers
-  const bool staged = STG > 1 && !RSTG && (!BVH || NIB || (kp.flags & KF_STAGE) != 0u);
+  const bool staged = STG > 1 && (!BVH || NIB || (kp.flags & KF_STAGE) != 0u);
   float* stage = reinterpret_cast<float*>(lds) + threadIdx.x * (WPS * STG);
   // DEFER kernels (<= kDeferMaxPrims primitives) always hold the attenuations in LDS, and
   // the 8-B-record kernels (<= kNibbleMaxPrims) the records too: compile-time facts there,
@@ -522,7 +474,6 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(FR_NUM_SGPR)
   uint32_t sbest = 0, s = 0, s_end = 0, nseg = 0, nhit = 0;  // (scatters = segments - samples: the host's)
   // (a sample's index within its block is s mod kBlockSamples: blocks start at multiples of it)
   static_assert((kBlockSamples & (kBlockSamples - 1u)) == 0u, "blocks of a power-of-two sample count");
-  V3 pend{0.0f, 0.0f, 0.0f};  // RSTG: the pair's first colour (an even jj)
 #ifdef FR_DIAG
   uint32_t diag_tb = 0, diag_seg0 = 0;  // the item's batch index, segments at its claim
   uint32_t diag_iter = 0;               // loop iterations of this wave
@@ -554,14 +505,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(FR_NUM_SGPR)
   // first claims at once on one counter would queue for ~80 us (about 88 returning
   // atomics per us on one word, MI355X_MICROARCH.md "dequeue").
   {
-#if defined(__HIP_DEVICE_COMPILE__)
-    typedef __attribute__((address_space(4))) const KArgs cargs_0;
-    cargs_0* ap0 = (cargs_0*)(__builtin_amdgcn_kernarg_segment_ptr());
-    asm volatile("" : "+s"(ap0));
-    const KParams k0 = ap0->kp;
-#else
-    const KParams& k0 = kp;
-#endif
+    const KParams k0 = kernarg_reload(args, [](const auto& a) { return a.kp; });
     q_next = (blockIdx.x * (kBlock / 64u) + (tid >> 6)) * kBatch;
     q_end = q_next + kBatch;
     uint32_t bb, qq, xx, yy;
@@ -615,16 +559,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(FR_NUM_SGPR)
         if (static_cast<int>(lane) == first) base = atomicAdd(kw.queue, kBatch);
         base = __builtin_amdgcn_readlane(base, first);
         // A slot past the image or the queue gets a stream that is never used.
-#if defined(__HIP_DEVICE_COMPILE__)
         // the item split's parameters reloaded from the kernarg segment here (once per 64
         // items) rather than held in SGPRs across the loop, like the camera (step 1)
-        typedef __attribute__((address_space(4))) const KArgs cargs_g;
-        cargs_g* apg = (cargs_g*)(__builtin_amdgcn_kernarg_segment_ptr());
-        asm volatile("" : "+s"(apg));
-        const KParams kg = apg->kp;
-#else
-        const KParams& kg = kp;
-#endif
+        const KParams kg = kernarg_reload(args, [](const auto& a) { return a.kp; });
         base += kg.n_static;  // past the waves' first batches
         q_end = base + kBatch;
         uint32_t bb, qq, xx, yy;
@@ -698,8 +635,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(FR_NUM_SGPR)
     PROF_MARK(PF_CLAIM);
     bool ended = false;
     V3 term{0.0f, 0.0f, 0.0f};
-    uint32_t tsky = kDeferAbsorbed;  // DEFER: the terminal as sky parameter bits (SKYD: dot(d, d))
-    float sky_dy = 0.0f;             // SKYD: the escaping ray's d.y
+    uint32_t tsky = kDeferAbsorbed;  // DEFER: the terminal as sky parameter bits
     if (need != NEED_NONE) {
       SEC(SC_NEED);
       // 1. merged rejection loop
@@ -762,17 +698,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(FR_NUM_SGPR)
         if (!lane_in(msph)) {
           SEC(SC_CAM);
           // Camera::get_ray (camera.rs:62-72)
-#if !defined(FR_CAM_RESIDENT) && defined(__HIP_DEVICE_COMPILE__)
           // scalar loads of the camera from the kernarg segment, here, rather than 19
-          // SGPRs held (and spilled) across the loop: the pointer is opaque to the
-          // compiler, so the loads stay in this step
-          typedef __attribute__((address_space(4))) const KArgs cargs;
-          cargs* ap = (cargs*)(__builtin_amdgcn_kernarg_segment_ptr());
-          asm volatile("" : "+s"(ap));
-          const KCam cm = ap->cam;
-#else
-          const KCam& cm = args.cam;
-#endif
+          // SGPRs held (and spilled) across the loop
+          const KCam cm = kernarg_reload(args, [](const auto& a) { return a.cam; });
           const V3 cpos{cm.px, cm.py, cm.pz}, cllc{cm.lx, cm.ly, cm.lz}, chor{cm.hx, cm.hy, cm.hz};
           const V3 cver{cm.vx, cm.vy, cm.vz}, cu{cm.ux, cm.uy, cm.uz}, cv{cm.bx, cm.by, cm.bz};
           // lens * (k 2^-23) = (lens 2^-23) * k when lens 2^-23 is exact (KCam::lens_pre):
@@ -819,22 +747,18 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(FR_NUM_SGPR)
       ++nseg;
       V3 inv{recip_nr(d.x), recip_nr(d.y), recip_nr(d.z)};
       // (non-short-circuit: one branch to the rare fallback instead of three nested ones)
-      // FR_BOX_FMA: the box test's reciprocal is RN(1 / d) clamped to +-2^100 (rt_core.h
-      // box_inv): recip_nr's range is narrowed to |d| >= 2^-100, where the clamp is the
-      // identity, and the fallback clamps
-      const int rok = FR_BOX_FMA ? static_cast<int>(recip_box_ok(d.x)) & static_cast<int>(recip_box_ok(d.y)) &
-                                       static_cast<int>(recip_box_ok(d.z))
-                                 : static_cast<int>(recip_nr_ok(d.x)) & static_cast<int>(recip_nr_ok(d.y)) &
-                                       static_cast<int>(recip_nr_ok(d.z));
+      // the box test's reciprocal is RN(1 / d) clamped to +-2^100 (rt_core.h box_inv):
+      // recip_nr's range is narrowed to |d| >= 2^-100, where the clamp is the identity, and
+      // the fallback clamps
+      const int rok = static_cast<int>(recip_box_ok(d.x)) & static_cast<int>(recip_box_ok(d.y)) &
+                      static_cast<int>(recip_box_ok(d.z));
       if (!rok) {
         inv = V3{1.0f / d.x, 1.0f / d.y, 1.0f / d.z};
-        if (FR_BOX_FMA) inv = V3{box_inv_clamp(inv.x), box_inv_clamp(inv.y), box_inv_clamp(inv.z)};
+        inv = V3{box_inv_clamp(inv.x), box_inv_clamp(inv.y), box_inv_clamp(inv.z)};
       }
-      const V3 boinv{o.x * inv.x, o.y * inv.y, o.z * inv.z};  // (FR_BOX_FMA box tests only)
+      const V3 boinv{o.x * inv.x, o.y * inv.y, o.z * inv.z};  // (box tests only)
       const float a_dd = dot(d, d);
-#ifndef FR_SPHERE_IEEE
       const SphereSeg ssg = sphere_seg(a_dd);  // unused (removed) in kernels without spheres
-#endif
       float closest = FLT_MAX, t_last = 0.0f;
       int best = -1;
       // The node cull is conservative only for origins within kBvhOriginReach scene
@@ -948,20 +872,19 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(FR_NUM_SGPR)
                 node_pick(slab3_fused(xyz(na), xyz(nb), oinv, invc),
                           slab3_fused(V3{na.w, nc.x, nc.y}, V3{nb.w, nc.z, nc.w}, oinv, invc), cl, cr);
               };
-#if FR_BVH_SCALAR_NODES
               const uint32_t ref0 = __builtin_amdgcn_readfirstlane(ref);
               if (__ballot(ref != ref0) == 0) {
                 // every walking lane is at the same node (90 % of C5's node steps): scalar
                 // loads, the slab arithmetic on SGPR operands (the distinct asm ends keep the
-                // two paths from being merged over copies of the node into VGPRs)
+                // two paths from being merged over copies of the node into VGPRs). With vector
+                // loads only, C5 trace 52.9 -> 62.3 ms: the vector memory path returns 64 B
+                // per lane per step
                 const RecRef nd = rec_at(sc.bvh, ref0);
                 const float4 r = nd[3];
                 SEC(SC_NODES);
                 node_step(nd[0], nd[1], nd[2], __float_as_uint(r.x), __float_as_uint(r.y));
                 asm volatile("; bvh node step: scalar");
-              } else
-#endif
-              {
+              } else {
                 SEC(SC_NODEV);
                 const uint32_t nb0 = ref * 64u;  // node byte offset (< 2^32: nodes < 2^26)
                 const uint4 nr = __builtin_bit_cast(uint4, buf_load4(sc.bvh, nb0 + 48u));
@@ -988,15 +911,11 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(FR_NUM_SGPR)
               bool h = false;
               if (k == FR_SPHERE) {
                 const float4 g = r[0];  // centre, RN(radius^2) (the leaf records' form)
-#ifndef FR_SPHERE_IEEE
                 const SphereDisc q = sphere_disc_rr(xyz(g), g.w, o, d, a_dd);
                 if (q.disc > 0.0f) {
                   SEC(SC_LROOT);
                   h = sphere_roots_fast(q, a_dd, ssg, 0.001f, tmax, t);
                 }
-#else
-                h = sphere_root_rr(xyz(g), g.w, o, d, a_dd, 0.001f, tmax, t);
-#endif
               } else if (k == FR_AABB) {
                 h = slab_root(slab3_box(xyz(r[0]), xyz(r[1]), o, inv, boinv), 0.001f, tmax, t);
               } else if (k == FR_TRIANGLE) {
@@ -1014,7 +933,6 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(FR_NUM_SGPR)
             };
             const uint32_t first = ref & ((1u << kBvhSlotBits) - 1u);
             const uint32_t cnt = ((ref >> kBvhSlotBits) & 15u) + 1u;
-#if FR_BVH_SCALAR_LEAVES
             const uint32_t leaf0 = __builtin_amdgcn_readfirstlane(ref);
             if (__ballot(ref != leaf0) == 0) {
               // every lane at one leaf: its records through scalar loads
@@ -1027,9 +945,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(FR_NUM_SGPR)
                 leaf_test(ord[first0 + kk], rec_at(sc.lrec, first0 + kk));
               }
               asm volatile("; bvh leaf: scalar");
-            } else
-#endif
-            {
+            } else {
               for (uint32_t kk = 0; kk < cnt; ++kk) {
                 SEC(SC_LTESTV);
                 const uint32_t slot = first + kk;
@@ -1058,11 +974,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(FR_NUM_SGPR)
           h = slab_root(slab3_box(xyz(r4[0]), xyz(r4[1]), o, inv, boinv), 0.001f, closest, t);
         } else if constexpr (K == FR_SPHERE) {
           const float4 g = r4[0];
-#ifndef FR_SPHERE_IEEE
           h = sphere_root_fast(xyz(g), g.w, o, d, a_dd, ssg, 0.001f, closest, t);
-#else
-          h = sphere_root(xyz(g), g.w, o, d, a_dd, 0.001f, closest, t);
-#endif
         } else if constexpr (K == FR_PLANE) {
           const int r = plane_test(xyz(r4[0]), xyz(r4[1]), xyz(r4[2]), o, d, 0.001f, closest, t);
           if (r) t_last = t;
@@ -1084,7 +996,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(FR_NUM_SGPR)
         // test; otherwise the compiler sinks the chain of selects into the shading step and
         // keeps every test's hit mask and t live until then (a 43-primitive list spilled
         // 64 SGPRs and 62 VGPRs)
-        if constexpr (FR_JIT_PIN && !std::is_same<typename std::decay<decltype(r4)>::type, RecRef>::value) {
+        if constexpr (!std::is_same<typename std::decay<decltype(r4)>::type, RecRef>::value) {
           asm volatile("" : "+v"(best));
           if (HAS_PLANE) asm volatile("" : "+v"(t_last));
         }
@@ -1106,15 +1018,6 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(FR_NUM_SGPR)
         auto test_j = [&](auto ic) {
           constexpr uint32_t I = decltype(ic)::value;
           constexpr uint32_t K = kJitRec[I][15];
-#if defined(__HIP_DEVICE_COMPILE__)
-          // Every FR_JIT_GROUP tests, the ray passes through an empty asm: later tests
-          // compute from new (equal) values, so terms are shared only within a group. A
-          // shared term is held in a register until its last use; across a 43-primitive
-          // list that spilled 62 VGPRs.
-          if constexpr (I > 0 && I % FR_JIT_GROUP == 0)
-            asm volatile("" : "+v"(o.x), "+v"(o.y), "+v"(o.z), "+v"(d.x), "+v"(d.y), "+v"(d.z), "+v"(inv.x),
-                         "+v"(inv.y), "+v"(inv.z));
-#endif
           if constexpr (K == FR_AABB || K == FR_SPHERE || K == FR_PLANE || K == FR_TRIANGLE || K == FR_OBB) {
             test_rec(std::integral_constant<uint32_t, K>{}, I, JitRec<I>{});
           }
@@ -1123,7 +1026,6 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(FR_NUM_SGPR)
         unroll_below<0u, FR_JIT_N>(FR_JIT_N, test_j);
       } else
 #endif
-#ifndef FR_NO_UNROLL_NIB
       if constexpr (NIB && !BVH && KS != KS_ANY) {
         // <= kNibbleMaxPrims primitives: the tests unrolled over the compile-time bound with
         // an exit at n, each index an inline constant (the winner select needs no index
@@ -1142,9 +1044,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(FR_NUM_SGPR)
         asm volatile("" : "+s"(n_here));
 #endif
         unroll_below<0u, kNibbleMaxPrims>(n_here, test_k);
-      } else
-#endif
-      if constexpr (KS != KS_ANY) {
+      } else if constexpr (KS != KS_ANY) {
         for (uint32_t ii = 0; ii < (list_walk ? sc.n : 0u); ++ii) {
           // the index is wave-uniform; say so, or the compiler may fall back to vector loads
           const uint32_t i = __builtin_amdgcn_readfirstlane(ii);
@@ -1181,18 +1081,11 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(FR_NUM_SGPR)
       SEC(SC_POSTHIT);
       if (best < 0) {
         SEC(SC_SKY);
-        if (SKYD) {
-          sky_dy = d.y;
-          tsky = __float_as_uint(d.x * d.x + d.y * d.y + d.z * d.z);  // length()'s sum, in its order
-        } else if (DEFER)
-#ifndef FR_SKY_IEEE
+        if (DEFER)
           // the sqrt and division by their core sequences under a range guard (sky_t_fast,
-          // bit-identical): C3 frame 15.52 -> 15.27 ms (in round 3, before the sum ran beside
-          // the trace, it had measured neutral); FR_SKY_IEEE builds the compiler's sequences
+          // bit-identical to sky_t): C3 frame 15.52 -> 15.27 ms (in round 3, before the sum
+          // ran beside the trace, it had measured neutral)
           tsky = __float_as_uint(sky_t_fast(d));  // tracer.rs:211-218, the blend in sum_kernel
-#else
-          tsky = __float_as_uint(sky_t(d));  // tracer.rs:211-218, the blend in sum_kernel
-#endif
         else
           term = sky(d);  // tracer.rs:211-218
         ended = true;
@@ -1285,10 +1178,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(FR_NUM_SGPR)
       DIAG_WAVE(DG_END_W);
       DIAG_LANE(DG_END_L);
       V3 col = term;
-      if (SKYD) {
-        col = V3{sky_dy, __uint_as_float(tsky), __uint_as_float(wnib)};
-        wnib = ~0u;  // the next sample starts empty
-      } else if (NIB) {
+      if (NIB) {
         col = V3{__uint_as_float(tsky), __uint_as_float(wnib), 0.0f};
         wnib = ~0u;  // the next sample starts empty
       } else if (DEFER) {
@@ -1331,77 +1221,30 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(FR_NUM_SGPR)
         }
       }
       const uint32_t jj = s & (kBlockSamples - 1u);  // the sample's index in its block
-      if (RSTG) {
-        // pairs start on even jj (blocks and sub-blocks do): the odd sample stores both
-        if (jj & 1u) {
-          float* dst = out + WPS * (jj - 1u);
-          if (kp.ks == kBlockSamples) {
-            if constexpr (WPS == 3u) {
-              // 8-B aligned: item * 192 B + a multiple of 24 B
-              reinterpret_cast<float2*>(dst)[0] = make_float2(pend.x, pend.y);
-              reinterpret_cast<float2*>(dst)[1] = make_float2(pend.z, col.x);
-              reinterpret_cast<float2*>(dst)[2] = make_float2(col.y, col.z);
-            } else {
-              // 16-B aligned: item * 128 B + a multiple of 16 B
-              *reinterpret_cast<float4*>(dst) = make_float4(pend.x, pend.y, col.x, col.y);
-            }
-          } else {
-            dst[0] = pend.x;
-            dst[1] = pend.y;
-            if (WPS == 3) dst[2] = pend.z;
-            dst[WPS] = col.x;
-            dst[WPS + 1] = col.y;
-            if (WPS == 3) dst[WPS + 2] = col.z;
-          }
-        } else if (s + 1u == s_end) {
-          out[WPS * jj] = col.x;
-          out[WPS * jj + 1] = col.y;
-          if (WPS == 3) out[WPS * jj + 2] = col.z;
-        } else {
-          pend = col;
-        }
-      } else if (!staged) {
+      if (!staged) {
         out[WPS * jj] = col.x;
         out[WPS * jj + 1] = col.y;
         if (WPS == 3) out[WPS * jj + 2] = col.z;
       } else {
-        // stage the colour; every STG-th sample of the block, and its last, go out together.
-        // FR_STAGE_SMAJOR (8-B records): slot-major staging, slot j of every lane of the
-        // workgroup contiguous (a wave's writes conflict-free) instead of each lane's
-        // STG slots contiguous (lanes 8 apart on one bank)
-        constexpr bool SMAJ = FR_STAGE_SMAJOR != 0 && WPS == 2u && STG == 4u;
-        float* const stage_base = reinterpret_cast<float*>(lds);
-        auto slot_at = [&](uint32_t js) -> float* {
-          return SMAJ ? stage_base + (js * kBlock + tid) * WPS : stage + WPS * js;
-        };
-        float* sl = slot_at(jj & (STG - 1u));
+        // stage the colour; every STG-th sample of the block, and its last, go out together
+        // (a group never spans sub-blocks: kparams.h)
+        float* sl = stage + WPS * (jj & (STG - 1u));
         sl[0] = col.x;
         sl[1] = col.y;
         if (WPS == 3) sl[2] = col.z;
         const bool full = (jj & (STG - 1u)) == STG - 1u;
         if (full || s + 1u == s_end) {
-          const uint32_t g0 = jj & ~(STG - 1u);
-          // (a sub-block inside a wider group stores from its own first sample)
-          // (its first sample: items of block b_fine are the 4-aligned sub-blocks, derived
-          // here rather than held in a register through the loop)
-          const bool fine_item = kStageSpansSub && kp.b_fine != 0u && s / kBlockSamples == kp.b_fine;
-          const uint32_t lo = fine_item ? (jj & ~(kFineSamples - 1u)) : g0;
-          float* dst = out + WPS * g0;
-          if (full && kp.ks == kBlockSamples && lo == g0) {
-            if constexpr (SMAJ) {
-              // two slots per 16-B store
-              const float2 a0 = *reinterpret_cast<const float2*>(slot_at(0)), a1 = *reinterpret_cast<const float2*>(slot_at(1));
-              const float2 a2 = *reinterpret_cast<const float2*>(slot_at(2)), a3 = *reinterpret_cast<const float2*>(slot_at(3));
-              reinterpret_cast<float4*>(dst)[0] = make_float4(a0.x, a0.y, a1.x, a1.y);
-              reinterpret_cast<float4*>(dst)[1] = make_float4(a2.x, a2.y, a3.x, a3.y);
-            } else if constexpr ((WPS * STG) % 4u == 0u) {
+          float* dst = out + WPS * (jj & ~(STG - 1u));
+          if (full && kp.ks == kBlockSamples) {
+            if constexpr ((WPS * STG) % 4u == 0u) {
               // 16-B aligned: item * 192 (128) B + a multiple of 48 (32) B
               const float4* src = reinterpret_cast<const float4*>(stage);
 #pragma unroll
               for (uint32_t k = 0; k < WPS * STG / 4u; ++k) {
                 reinterpret_cast<float4*>(dst)[k] = src[k];
 #if defined(__HIP_DEVICE_COMPILE__)
-                // wide groups: two 16-B stores at a time, not every LDS read first (registers)
+                // 12-B records (three stores): each 16-B store follows its LDS read, not every
+                // read first (registers)
                 if (WPS * STG > 8u) asm volatile("" ::: "memory");
 #endif
               }
@@ -1412,8 +1255,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(FR_NUM_SGPR)
               for (uint32_t k = 0; k < WPS * STG / 2u; ++k) reinterpret_cast<float2*>(dst)[k] = src[k];
             }
           } else {
-            for (uint32_t k = WPS * (lo - g0); k < WPS * ((jj & (STG - 1u)) + 1u); ++k)
-              dst[k] = SMAJ ? slot_at(k / WPS)[k % WPS] : stage[k];
+            for (uint32_t k = 0; k < WPS * ((jj & (STG - 1u)) + 1u); ++k) dst[k] = stage[k];
           }
         }
       }

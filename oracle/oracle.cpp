@@ -327,7 +327,7 @@ struct Stub : Hitable {
 
 // ---- build-defined box, restated from its written spec ------
 // Slabs per axis k: t0 = (lo_k - o_k) * (1/d_k), t1 = (hi_k - o_k) * (1/d_k) (the oriented
-// box; the axis-aligned one computes them as Aabb::slabs_fma does, OR_BOX_FMA);
+// box; the axis-aligned one computes them as Aabb::slabs_fma does);
 // near_k = fminf(t0, t1), far_k = fmaxf(t0, t1) (C99 fmin/fmax: NaN-ignoring);
 // tn = fmaxf(fmaxf(near_x, near_y), near_z), tf = fminf(fminf(far_x, far_y), far_z).
 // Hit iff tn < tf; then the near root if it is in (t_min, t_max), else the far root
@@ -377,14 +377,11 @@ struct BoxBase : Hitable {
   }
 };
 
-#ifndef OR_BOX_FMA
-#define OR_BOX_FMA 1  // the box definition since round 6; 0: round 5's
-#endif
 struct Aabb : BoxBase {
   Vec3 mn, mx;
-  // OR_BOX_FMA: the axis-aligned box's slab distances as fmaf(lo_k, inv_k, -(o_k * inv_k))
-  // with inv_k = RN(1 / d_k) clamped to [-2^100, 2^100] (fmaxf, then fminf), the rest as
-  // slabs() (the product's FR_BOX_FMA)
+  // The box definition since round 6: the axis-aligned box's slab distances
+  // as fmaf(lo_k, inv_k, -(o_k * inv_k)) with inv_k = RN(1 / d_k) clamped to [-2^100, 2^100]
+  // (fmaxf, then fminf), the rest as slabs() (the product's slab3_box)
   static bool slabs_fma(Vec3 lo, Vec3 hi, Vec3 o, Vec3 d, float t_min, float t_max, float& t, Vec3& n_local) {
     float t0[3], t1[3], nr[3], fr[3];
     for (int k = 0; k < 3; ++k) {
@@ -418,9 +415,7 @@ struct Aabb : BoxBase {
   bool hit(Ray ray, float t_min, float t_max, HitRecord& rec) const override {
     float t;
     Vec3 n;
-    const bool h = OR_BOX_FMA ? slabs_fma(mn, mx, ray.origin(), ray.direction(), t_min, t_max, t, n)
-                              : slabs(mn, mx, ray.origin(), ray.direction(), t_min, t_max, t, n);
-    if (!h) return false;
+    if (!slabs_fma(mn, mx, ray.origin(), ray.direction(), t_min, t_max, t, n)) return false;
     rec.t = t;
     rec.p = ray.point_at(t);
     rec.normal = n;

@@ -11,6 +11,8 @@
 //   plan_check kernels             every specialisation select_kernel can reach, once each
 //   plan_check strips H COUNT      the strip geometry of each shard, plain and MT bands
 //   plan_check pack FILE...        each scene file (or "empty") through pack_scene
+//   plan_check tuning              tuning_defines(): this build's tuning values as the #define
+//                                  lines the scene kernel's run-time build starts with (plain text)
 // One JSON line per case on stdout.
 #include <stdint.h>
 #include <stdio.h>
@@ -82,13 +84,13 @@ static int do_plan(int argc, char** argv) {
          "\"defer\": %d, \"nibble\": %d, \"diffuse_k\": %d, \"bvh_nib\": %d, \"wps\": %u, \"per_block\": %zu, "
          "\"nblocks\": %u, \"nb_pass\": %u, \"cap_blocks\": %zu, \"passes\": %d, \"nfs\": %d, \"fpipe\": %d, "
          "\"overlap\": %d, \"stream_mode\": %d, \"relayout\": %d, \"reserve\": %u, \"slot_bytes\": %zu, \"slots\": %d, "
-         "\"running_bytes\": %zu, \"lds\": %zu, \"stage_bytes\": %zu, \"sum_kind\": %d, \"jit_on\": %d, "
+         "\"running_bytes\": %zu, \"lds\": %zu, \"stage_bytes\": %zu, \"jit_on\": %d, "
          "\"jit_wait\": %d, \"jit_cached_only\": %d, \"bvh_stage\": %d, \"max_wgs\": %u, \"kernel\": \"%s\", "
          "\"targs\": [%d, %d, %d, %d, %d, %d, %d, %d], \"pass\": [",
          kp.P, kp.n_tiles, kp.ks, kp.flags, fp.use_bvh, fp.small_depth, fp.defer, fp.nibble, fp.diffuse_k, fp.bvh_nib,
          fp.wps, fp.per_block, fp.nblocks, fp.nb_pass, fp.cap_blocks, fp.passes, fp.nfs, fp.fpipe, fp.fpipe_overlap,
          fp.stream_mode, fp.relayout, fp.reserve, fp.slot_bytes, fp.slots, fp.running_bytes, fp.lds, fp.stage_bytes,
-         fp.sum_kind, fp.jit_on, fp.jit_wait, fp.jit_cached_only, fp.bvh_stage, fp.max_wgs, id.name.c_str(), id.targs[0],
+         fp.jit_on, fp.jit_wait, fp.jit_cached_only, fp.bvh_stage, fp.max_wgs, id.name.c_str(), id.targs[0],
          id.targs[1], id.targs[2], id.targs[3], id.targs[4], id.targs[5], id.targs[6], id.targs[7]);
   for (int pass = 0; pass < fp.passes; ++pass) {
     const fr::PassPlan pp = fr::pass_plan(fp, pass);
@@ -187,11 +189,12 @@ int main(int argc, char** argv) {
   if (argc == 2 && strcmp(argv[1], "kernels") == 0) return do_kernels();
   if (argc == 4 && strcmp(argv[1], "strips") == 0)
     return do_strips(static_cast<uint32_t>(atoi(argv[2])), static_cast<uint32_t>(atoi(argv[3])));
+  if (argc == 2 && strcmp(argv[1], "tuning") == 0) return fputs(fr::tuning_defines().c_str(), stdout) < 0;
   if (argc >= 3 && strcmp(argv[1], "pack") == 0) {
     for (int i = 2; i < argc; ++i)
       if (do_pack(argv[i])) return 2;
     return 0;
   }
-  fprintf(stderr, "usage: %s plan KEY=VALUE... | kernels | strips H COUNT | pack FILE...\n", argv[0]);
+  fprintf(stderr, "usage: %s plan KEY=VALUE... | kernels | strips H COUNT | pack FILE... | tuning\n", argv[0]);
   return 2;
 }

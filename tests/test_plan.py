@@ -22,14 +22,18 @@ KNOBS = ("FR_BVH", "FR_DEFER", "FR_MAT", "FR_PIPELINE", "FR_SAMPLE_BUFFER_GB", "
          "FR_FRAME_PIPE_RESERVE", "FR_SCENE_JIT", "FR_BVH_STAGE", "FR_MAX_WGS")
 
 
-@pytest.fixture(scope="module")
-def exe(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("plan") / "plan_check")
+def _build_plan_check(out, defs=()):
     srcs = [os.path.join(ROOT, "tests", "c", "plan_check.cpp")] + [
         os.path.join(ROOT, "fo-rma_amd", "csrc", f) for f in ("plan.cpp", "pack.cpp", "json_min.cpp", "scene.cpp", "bvh.cpp")]
     subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-fno-omit-frame-pointer", "-ffp-contract=off", "-fno-fast-math", "-pthread",
+                    "-fno-omit-frame-pointer", "-ffp-contract=off", "-fno-fast-math", "-pthread", *defs,
                     "-I", os.path.join(ROOT, "include"), *srcs, "-o", out], check=True, timeout=600)
+
+
+@pytest.fixture(scope="module")
+def exe(tmp_path_factory):
+    out = str(tmp_path_factory.mktemp("plan") / "plan_check")
+    _build_plan_check(out)
     return out
 
 
@@ -237,3 +241,86 @@ def test_packed_scenes(exe, tmp_path):
     empty, gen10k = res[-2], res[-1]
     assert empty["n"] == 0 and empty["rec0_kind"] == STUB and empty["n_aclass"] == 0
     assert gen10k["n"] == 10000 and gen10k["bvh_ok"] == 1 and gen10k["n_segs"] >= 1 and gen10k["bvh_levels"] <= 16
+
+
+# ---- the tuning table (fo-rma_amd/csrc/tuning.h) ------------------------------------------
+
+CSRC = os.path.join(ROOT, "fo-rma_amd", "csrc")
+# build macros and identifiers retired with the A/B alternatives they selected (profiles/AB_LOG.md
+# keeps the measurements). FR_BVH_STAGE is not listed: the environment knob of that name stays.
+RETIRED = ("FR_STAGE_SMAJOR FR_BVH_RSTAGE FR_TRACE_PRIO FR_CAM_RESIDENT FR_SPHERE_IEEE FR_SKY_IEEE FR_NO_UNROLL_NIB "
+           "FR_BVH_SCALAR_NODES FR_BVH_SCALAR_LEAVES FR_JIT_PIN FR_JIT_GROUP FR_SKY_DEFER FR_STAGE FR_BLOCK_SAMPLES "
+           "FR_FINE_SAMPLES FR_SUM_UNROLL_SKYD FR_SKY_SUM_IEEE FR_XOSHIRO_PLAIN FR_DIV_2STEP FR_BOX_FMA OR_BOX_FMA "
+           "FR_SUM_PRIO FR_SUM_STUB FR_SUM_BUFLOAD FR_SUM_WAITFIX FR_SUM_DIRECT FR_SUM_THREADS FR_SUM_VGPRS "
+           "FR_SETUP_ON_TRACE_STREAM FR_QUEUE_MEMSET FR_TAIL_PRIO FR_KLENS FR_KSCAT kSkyDefer SKYD sky_dy RSTG SMAJ "
+           "slot_at stage_base kStageSpansSub fine_item sum_kind jit_defines").split()
+TEXT = (".h", ".hip", ".cpp", ".py", ".sh", ".md", ".txt", ".json", ".inc")
+
+
+def _tuning_header():
+    """tuning.h's defaults {name: value text} in file order, and FR_TUNING's names in list order."""
+    text = open(os.path.join(CSRC, "tuning.h")).read()
+    defaults = re.findall(r"^#ifndef (FR_\w+)\n#define \1 (\S+)[^\n]*\n#endif$", text, re.M)
+    assert len(defaults) == len(re.findall(r"^#\s*ifndef\b", text, re.M)), "an #ifndef that is not a default"
+    (body,) = re.findall(r"^#define FR_TUNING\(X\)((?:[^\n]*\\\n)*[^\n]*)$", text, re.M)
+    return dict(defaults), [n for n, _ in defaults], re.findall(r"X\((\w+)\)", body)
+
+
+def _default_value(defaults, name):
+    v = defaults[name]
+    return int(v) if re.fullmatch(r"\d+", v) else _default_value(defaults, v)  # (a default may name another knob)
+
+
+def _source_files(*tops):
+    for top in tops:
+        for d, dirs, files in os.walk(os.path.join(ROOT, top)):
+            dirs[:] = [x for x in dirs if x not in ("build", "_ref", "__pycache__", "sessions")]
+            for f in files:
+                if f.endswith(TEXT) or f == "Makefile":
+                    yield os.path.join(d, f)
+
+
+def test_tuning_table_names_every_default_once():
+    defaults, order, listed = _tuning_header()
+    assert len(order) == len(set(order))
+    assert sorted(listed) == sorted(order) and len(listed) == len(set(listed))
+    for path in _source_files(os.path.join("fo-rma_amd", "csrc")):
+        if os.path.basename(path) != "tuning.h":
+            assert "#ifndef FR_" not in open(path).read(), path
+
+
+def test_retired_names_are_gone():
+    pat = re.compile(r"\b(" + "|".join(RETIRED) + r")\b")
+    for path in _source_files("fo-rma_amd", "oracle", "tools"):
+        text = open(path, errors="replace").read()
+        if path == os.path.join(CSRC, "plan.h"):  # FramePlan's one inert member (see its comment), nothing else
+            text = text.replace("  int sum_kind = 0;\n", "", 1)
+        m = pat.search(text)
+        assert not m, (path, m.group(0))
+    # ("pend" is also a word: only the kernel that held the variable is searched for it)
+    assert not re.search(r"\bpend\b", open(os.path.join(CSRC, "trace_kernel.h")).read())
+
+
+def _defines(exe):
+    base = {k: v for k, v in os.environ.items() if k not in KNOBS}
+    p = subprocess.run([exe, "tuning"], capture_output=True, text=True, timeout=600, env=base)
+    assert p.returncode == 0 and "Sanitizer" not in p.stderr and "runtime error" not in p.stderr, p.stderr[-4000:]
+    lines = p.stdout.splitlines()
+    assert all(re.fullmatch(r"#define FR_\w+ -?\d+", ln) for ln in lines), lines
+    return [(ln.split()[1], int(ln.split()[2])) for ln in lines]
+
+
+def test_tuning_defines_forward_every_default(exe):
+    defaults, order, listed = _tuning_header()
+    assert _defines(exe) == [(n, _default_value(defaults, n)) for n in listed]
+    assert "sum_kind" not in _plan(exe, **HEADLINE)  # (left the printout with the 12-byte sky record)
+
+
+def test_tuning_defines_forward_a_variant_builds_values(tmp_path):
+    """One valued knob, one that was never forwarded, and the one that was a presence flag."""
+    over = {"FR_KREJ_NIB": 7, "FR_BVH_WAVES": 6, "FR_MIN_WAVES": 5}
+    out = str(tmp_path / "plan_check_variant")
+    _build_plan_check(out, [f"-D{k}={v}" for k, v in over.items()])
+    defaults, order, listed = _tuning_header()
+    assert _defines(out) == [(n, over.get(n, _default_value(defaults, n))) for n in listed]
+

@@ -22,9 +22,11 @@ mkdir -p "$root/fo-rma_amd/build/ab"
 # embed REV's trace_kernel.h (and what it includes), so the A/B covers the hiprtc kernel too
 c="$tmp/fo-rma_amd/csrc"
 mkdir -p "$tmp/fo-rma_amd/build"
-kparams=""
-[ -f "$c/kparams.h" ] && kparams="kparams.h=$c/kparams.h"  # the launch contract's own header (once split out)
-python3 "$c/embed_sources.py" "$tmp/fo-rma_amd/build/jit_sources.inc" trace_kernel.h="$c/trace_kernel.h" $kparams \
+split=""  # the headers split out of trace_kernel.h, where REV has them: the launch contract, the tuning table
+for h in kparams.h tuning.h; do
+  [ -f "$c/$h" ] && split="$split $h=$c/$h"
+done
+python3 "$c/embed_sources.py" "$tmp/fo-rma_amd/build/jit_sources.inc" trace_kernel.h="$c/trace_kernel.h" $split \
   rt_core.h="$c/rt_core.h" bvh.h="$c/bvh.h" forma_rt.h="$tmp/include/forma_rt.h"
 HOST="g++ -O2 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -Wall -Wno-unused-function $defs"
 $HOST -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -c "$c/jit.cpp" -o "$tmp/jit.o"

@@ -1,7 +1,8 @@
 """Per-phase VALU breakdown of the headline trace kernel (the scene_08 scene-specialised build).
 
 Static side: trace_kernel.h is compiled the way jit.cpp's hiprtc build compiles it (same
-options, the host build's tuning macros, scene_08's records as constants), with
+options, csrc/tuning.h's defaults unless a -DNAME=V argument overrides one, scene_08's
+records as constants), with
 -DFR_SEC_MARKS, which turns every SEC(k) region marker of the lane loop into an assembler
 comment. The ISA listing is cut at those comments and each region's VALU instructions
 are counted (v_* opcodes; SALU, LDS and memory instructions separately).
@@ -33,9 +34,6 @@ REGIONS = ["SC_ITER", "SC_CLAIM", "SC_JIT", "SC_NEED", "SC_REJ", "SC_CAM", "SC_S
 # marker-only regions: the counted region whose entries they share
 DERIVED = {"SC_SETUP": "SC_CLAIM", "SC_ACC": "SC_NEED", "SC_POSTHIT": "SC_HIT", "SC_POSTSHADE": "SC_ITER",
            "SC_LATCH": "SC_ITER", "SC_NODET": "SC_NODE"}
-# render.hip jit_defines() for the default build
-DEFINES = dict(FR_KREJ=4, FR_KREJ_NIB=9, FR_CLAIM_MIN=1, FR_CLAIM_MIN_NIB=3, FR_NUM_SGPR=96, FR_BLOCK_SAMPLES=16,
-               FR_FINE_SAMPLES=4, FR_STAGE=4, FR_BVH_STAGE=2, FR_NIB_WAVES=8, FR_DIFF12_WAVES=7)
 OPTS = ["-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fhip-fp32-correctly-rounded-divide-sqrt",
         "-fno-gpu-flush-denormals-to-zero", "-fno-slp-vectorize"]
 
@@ -66,11 +64,7 @@ def scene_records(name="scene_08"):
 def build_isa(targs, extra_defs=(), jit=True, scene="scene_08", prelude_file=None):
     out = os.path.join(ROOT, "fo-rma_amd", "build", "isa_jit")
     os.makedirs(out, exist_ok=True)
-    defs = dict(DEFINES)
-    for a in extra_defs:  # -DNAME=V overrides the host build's value of NAME
-        if a.startswith("-D") and "=" in a and a[2:].split("=", 1)[0] in defs:
-            defs[a[2:].split("=", 1)[0]] = a.split("=", 1)[1]
-    pre = "".join(f"#define {k} {v}\n" for k, v in defs.items())
+    pre = ""  # (the tuning values: csrc/tuning.h's defaults, or the -DNAME=V of extra_defs)
     if jit:  # the scene-specialised build (scene_08's records); else the compiled-in kernel
         recs = scene_records(scene)
         pre += f"#define FR_JIT_N {len(recs)}u\n#define FR_JIT_REC " + ",".join(
@@ -84,7 +78,6 @@ def build_isa(targs, extra_defs=(), jit=True, scene="scene_08", prelude_file=Non
     with open(src, "w") as f:
         f.write(pre + '#include "trace_kernel.h"\n' + inst)
     asm = src[:-4] + ".s"
-    extra_defs = [a for a in extra_defs if not (a.startswith("-D") and "=" in a and a[2:].split("=", 1)[0] in defs)]
     cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "--cuda-device-only", "-S", "-I", CSRC, "-I",
            os.path.join(ROOT, "include"), *OPTS, *([] if os.environ.get("ISA_NOMARKS") else ["-DFR_SEC_MARKS"]),
            *extra_defs, src, "-o", asm]

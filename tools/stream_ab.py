@@ -60,7 +60,7 @@ def main():
     ap.add_argument("--shards", type=int, default=1)
     ap.add_argument("--shard", type=int, default=0)
     ap.add_argument("--allow-diff", action="append", default=[],
-                    help="variant whose frame may differ (a measurement-only build)")
+                    help="variant whose frame may differ (its hash is not checked)")
     a = ap.parse_args()
     specs = []
     for v in a.variants:
