@@ -120,4 +120,31 @@ static_assert(kStage <= kFineSamples && kBvhStage <= kFineSamples && kFineSample
                   kFineSamples % kBvhStage == 0,
               "a staging group never exceeds a sub-block");
 
+// Per-wave batch table (trace_kernel's claim step): when a wave seeds a batch
+// of 64 items, lane k stores everything item base + k needs to start as one 32-B entry in
+// LDS, and a claiming lane reads its entry back instead of deriving it.
+// Only the list kernels with 8-B records have the table: their LDS holds no stack and at
+// most kNibbleMaxPrims records (< 10 KB with the staging), so 8 KB more keeps every resident
+// workgroup. The other kernels' LDS is spoken for (unwind and traversal stacks, up to
+// kAttLds attenuations): they keep the batch in registers.
+constexpr uint32_t kBatchEntryBytes = 32;
+constexpr uint32_t kBatchTableBytes = kBlock * kBatchEntryBytes;  // 64 entries for each of the 4 waves
+FR_KHD_CONSTEXPR bool has_batch_table(bool bvh, bool nib) { return nib && !bvh; }
+// An entry: the item's four stream words, then {fx, fy, se, slot}:
+//   fx, fy  the jitter's numerator bases 2^24 x + 2^23 and 2^24 yrow + 2^23 (yrow = H - y);
+//   se      first sample | end sample << 8 | need << 16 | slot's bits 32.. << 24, samples
+//           counted from the start of the item's 16-sample block (the loop reads a sample's
+//           number only modulo kBlockSamples and against its end); need = kNeedJit for an
+//           item to trace. An entry past the image edge or the pass's items has first ==
+//           end == need == 0, as after an unsuccessful claim;
+//   slot    the item's first sample slot in the buffer, in samples: (item - k P) ks for
+//           sub-block k, below 2^36 (items are 32-bit, ks <= 16); its low 32 bits.
+struct BatchEntry {
+  uint32_t s0, s1, s2, s3;
+  float fx, fy;
+  uint32_t se, slot;
+};
+static_assert(sizeof(BatchEntry) == kBatchEntryBytes, "two 16-B LDS accesses per entry");
+constexpr uint32_t kNeedJit = 3;  // trace_kernel's NEED_JIT
+
 }  // namespace fr

@@ -188,6 +188,8 @@ int make_plan(const fr_params& p, float cam_reach, const SceneFacts& sf, int num
                                                     sizeof(uint32_t);
   const size_t n_rec = sf.n <= kRecLds ? sf.n : 0u;
   const size_t stage_n = stage_samples(fp.use_bvh, fp.nibble);
+  // the waves' batch tables, in front of everything else (trace_kernel.h): every launch adds them
+  fp.table_bytes = has_batch_table(fp.use_bvh, fp.nibble) ? kBatchTableBytes : 0u;
   fp.lds = (stage_n > 1 && (!fp.use_bvh || fp.nibble) ? kBlock * stage_n * fp.wps * sizeof(float) : 0u) +
            (n_att ? n_att + 1 : 0) * 16 + n_rec * 64 + stack_bytes +
            (fp.use_bvh ? (sf.bvh_levels + 1u) * kBlock * sizeof(uint32_t) : 0u);  // + the sentinel row

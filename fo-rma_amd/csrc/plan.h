@@ -146,6 +146,7 @@ struct FramePlan {
   int slots = 1;
   size_t lds = 0;
   size_t stage_bytes = 0;  // BVH kernels: LDS for sample staging, taken if it costs no residency
+  size_t table_bytes = 0;  // list kernels with 8-B records: LDS for the waves' batch tables (kparams.h)
   // always 0 (the record's form follows KParams.flags) and read by nothing here. It stays for
   // one reason: the previous revision's tests/c/plan_check.cpp prints it, and that revision's
   // tests are run against this library before it is accepted. Delete it with the next change.

@@ -280,7 +280,7 @@ struct Grid {
 template <class Kern>
 static Grid size_grid(Kern kern, hipFunction_t jfn, const FramePlan& fp, uint32_t n_items, int num_cus) {
   Grid g;
-  g.lds = fp.lds;
+  g.lds = fp.lds + fp.table_bytes;
   const hipError_t oe =
       jfn ? hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&g.per_cu, jfn, static_cast<int>(kBlock), g.lds)
           : hipOccupancyMaxActiveBlocksPerMultiprocessor(&g.per_cu, kern, static_cast<int>(kBlock), g.lds);

@@ -295,6 +295,52 @@ __host__ __device__ __forceinline__ uint32_t stream_key(uint32_t bw) {
   return (bw & kFineKey) ? (kFineKey | ((bw & 0x0FFFFFFFu) * kFineSub + ((bw >> 28) & 3u))) : bw;
 }
 
+// Everything a work item needs to start, as its batch-table entry (kparams.h BatchEntry):
+// computed by the lane that seeds the item's slot, once per 64 items at full width, so the
+// claim step only copies it. The divisions, integer multiplies and int-to-float
+// conversions of the item's pixel, sample range and buffer slot all happen here.
+__device__ __forceinline__ BatchEntry batch_entry(const KParams& kp, uint32_t item) {
+  uint32_t bw, q, x, y;
+  const bool in_image = item_xy(kp, item, bw, q, x, y);
+  const Rng st = rng_seed(kp.seed, y * kp.W + x, stream_key(bw));
+  // a sub-block k of block b_fine: samples [16 b + 4 k, +4) of the block's slot (item - k P
+  // in the buffer); a whole block: k = 0
+  const uint32_t k = (bw >> 28) & 3u;
+  const bool fine = (bw & kFineKey) != 0u;
+  const uint32_t first = k * kFineSamples;
+  const uint32_t left = kp.spp - (bw & 0x0FFFFFFFu) * kBlockSamples;  // the block's samples below spp
+  const uint32_t span = first + (fine ? kFineSamples : kBlockSamples);
+  const uint32_t end = span < left ? span : left;
+  const bool ok = in_image && item < kp.n_items;
+  BatchEntry e;
+  e.s0 = st.s0;
+  e.s1 = st.s1;
+  e.s2 = st.s2;
+  e.s3 = st.s3;
+  // 2^24 x + 2^23, exact (x, yrow < 2^23): the jitter's numerator bases (step 1);
+  // tracer.rs:171-172: v = ((H - y) + r) / H
+  e.fx = static_cast<float>(x) * 16777216.0f + 8388608.0f;
+  e.fy = static_cast<float>(kp.H - y) * 16777216.0f + 8388608.0f;
+  const uint64_t slot = static_cast<uint64_t>(item - k * kp.P) * kp.ks;
+  e.se = (ok ? (first | (end << 8) | (kNeedJit << 16)) : 0u) | (static_cast<uint32_t>(slot >> 32) << 24);
+  e.slot = static_cast<uint32_t>(slot);
+  return e;
+}
+
+// 16-B LDS accesses at a byte address (a batch-table entry is two)
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ __attribute__((address_space(3))) u32x4& lds_u32x4_at(uint32_t a) {
+  return *reinterpret_cast<__attribute__((address_space(3))) u32x4*>(static_cast<uintptr_t>(a));
+}
+// Orders this wave's LDS accesses across a point where lanes exchange data through LDS (the
+// batch table): no instruction, the LDS serves one wave's operations in order.
+__device__ __forceinline__ void wave_lds_order() {
+#if defined(__HIP_DEVICE_COMPILE__)
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+#endif
+}
+
 // Persistent path-tracing kernel. Work item = (pixel slot q, sample block b): the
 // kBlockSamples samples [16b, 16b + 16) of one pixel, drawn in order from the RNG
 // stream (seed, pixel, b). Each sample's colour goes to kw.samples; sum_kernel then
@@ -371,15 +417,19 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(FR_NUM_SGPR)
   //      [stack: MAXD ? kBlock x MAXD u16 (lane-major) : max_depth x kBlock u32]
   // Entry n of the attenuations is (1, 1, 1): the depth-8 stack's empty levels hold n.
   // Staging the winner's data keeps per-lane global gathers off the shading path.
-  // [STG > 1: kBlock x STG staged sample colours (12 B each), lane-major] in front.
+  // [STG > 1: kBlock x STG staged sample colours (12 B each), lane-major] in front,
+  // [TABLE: the waves' batch tables, 64 x 32-B entries each (kparams.h)] before all.
   extern __shared__ uint32_t lds[];
   constexpr bool NIB = DEFER == 2;             // 8-B records, winners in a register
   constexpr uint32_t STG = stage_samples(BVH, NIB);
   constexpr bool DIFFUSE = MAT == 1;           // lambertian scatters only
   constexpr uint32_t WPS = NIB ? 2u : 3u;      // words per sample in the buffer
+  constexpr bool TABLE = has_batch_table(BVH, NIB);
+  constexpr uint32_t TABW = TABLE ? kBatchTableBytes / 4u : 0u;  // the tables' words
+  static_assert(!TABLE || !MT, "a batch-table entry holds no render_mt band offset");
   // list kernels always stage; BVH kernels when the launch gave them the LDS (KF_STAGE)
   const bool staged = STG > 1 && (!BVH || NIB || (kp.flags & KF_STAGE) != 0u);
-  float* stage = reinterpret_cast<float*>(lds) + threadIdx.x * (WPS * STG);
+  float* stage = reinterpret_cast<float*>(lds) + TABW + threadIdx.x * (WPS * STG);
   // DEFER kernels (<= kDeferMaxPrims primitives) always hold the attenuations in LDS, and
   // the 8-B-record kernels (<= kNibbleMaxPrims) the records too: compile-time facts there,
   // so their global-load fallbacks are not compiled
@@ -390,7 +440,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(FR_NUM_SGPR)
   const uint32_t n_att = ATT_LDS || sc.n <= kAttLds ? sc.n : 0u;
   const uint32_t n_att_st = n_att ? n_att + 1u : 0u;  // with the unit entry
   const uint32_t n_rec = REC_LDS || sc.n <= kRecLds ? sc.n : 0u;
-  float4* att_lds = reinterpret_cast<float4*>(lds + (staged ? kBlock * WPS * STG : 0u));
+  float4* att_lds = reinterpret_cast<float4*>(lds + TABW + (staged ? kBlock * WPS * STG : 0u));
   float4* rec_lds = att_lds + n_att_st;
   uint32_t* stack = reinterpret_cast<uint32_t*>(rec_lds + 4u * n_rec);
   uint16_t* hstack = reinterpret_cast<uint16_t*>(stack);
@@ -445,6 +495,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(FR_NUM_SGPR)
   // NEED_JIT: a sample starts (its jitter, then its first lens try); NEED_LENS: a camera
   // lane's lens try after a rejected one
   enum : uint32_t { NEED_NONE = 0, NEED_LENS = 1, NEED_SPHERE = 2, NEED_JIT = 3 };
+  static_assert(NEED_JIT == kNeedJit && NEED_NONE == 0u, "a batch-table entry holds the claim's need");
   uint32_t depth = 0;  // scatters of the path (not NIB: wnib holds them)
   // NIB: the winners as 4-bit entries, the last one pushed in bits 28..31 and the first in
   // bits 32 - 4 depth .. 35 - 4 depth, 15 on the levels below (empty). sum_kernel multiplies
@@ -501,6 +552,16 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(FR_NUM_SGPR)
   // ... and the same slot's pixel (x | y << 16, all ones past the image edge) and sample
   // block, so a claiming lane fetches those by permute too instead of dividing the item
   uint32_t held_xy = 0xFFFFFFFFu, held_b = 0u;
+  // TABLE kernels hold none of these: the seeding lane goes on to everything else the item
+  // needs to start (batch_entry) and stores it as slot k of the wave's batch table in LDS,
+  // this lane's own entry at byte tid * 32 of the tables. A claiming lane reads its item's
+  // entry from there: no permutes, and no per-item setup in the few lanes that claim.
+  const uint32_t tab_mine = lds_addr(lds) + tid * kBatchEntryBytes;
+  auto seed_entry = [&](const KParams& kq, uint32_t item) {
+    const BatchEntry e = batch_entry(kq, item);
+    lds_u32x4_at(tab_mine) = u32x4{e.s0, e.s1, e.s2, e.s3};
+    lds_u32x4_at(tab_mine + 16u) = u32x4{__float_as_uint(e.fx), __float_as_uint(e.fy), e.se, e.slot};
+  };
   // A wave's first batch is its own (wave w of the grid: batch w), seeded here: 7168
   // first claims at once on one counter would queue for ~80 us (about 88 returning
   // atomics per us on one word, MI355X_MICROARCH.md "dequeue").
@@ -508,11 +569,16 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(FR_NUM_SGPR)
     const KParams k0 = kernarg_reload(args, [](const auto& a) { return a.kp; });
     q_next = (blockIdx.x * (kBlock / 64u) + (tid >> 6)) * kBatch;
     q_end = q_next + kBatch;
-    uint32_t bb, qq, xx, yy;
-    const bool in_image = item_xy(k0, q_next + lane, bb, qq, xx, yy);
-    held = rng_seed(k0.seed, yy * k0.W + xx, stream_key(bb));
-    held_xy = in_image ? (xx | (yy << 16)) : 0xFFFFFFFFu;
-    held_b = bb;
+    if constexpr (TABLE) {
+      seed_entry(k0, q_next + lane);
+      wave_lds_order();
+    } else {
+      uint32_t bb, qq, xx, yy;
+      const bool in_image = item_xy(k0, q_next + lane, bb, qq, xx, yy);
+      held = rng_seed(k0.seed, yy * k0.W + xx, stream_key(bb));
+      held_xy = in_image ? (xx | (yy << 16)) : 0xFFFFFFFFu;
+      held_b = bb;
+    }
   }
   while (active) {
     SEC(SC_ITER);
@@ -539,96 +605,171 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(FR_NUM_SGPR)
                                                    __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(m), 0u));
       const uint32_t next = __builtin_amdgcn_readfirstlane(q_next);
       const uint32_t avail = __builtin_amdgcn_readfirstlane(q_end) - next;
-      uint32_t base = 0;
-      const bool grab = n > avail;
-      const int first = __ffsll(static_cast<long long>(m)) - 1;
-      // The item's stream start, pixel and block, by lane permute from the lane that
-      // seeded them: first from the current batch (claims r < avail), then, after a grab,
-      // from the new batch (claims r >= avail). Every lane of the wave is active at both
-      // permutes (a permute reads 0 from an inactive source): a lane retires only after
-      // the queue has drained, and from then on no batch holds a valid item.
-      int sl = static_cast<int>(((next + r) & (kBatch - 1u)) << 2);
-      Rng st{static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(sl, static_cast<int>(held.s0))),
-             static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(sl, static_cast<int>(held.s1))),
-             static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(sl, static_cast<int>(held.s2))),
-             static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(sl, static_cast<int>(held.s3)))};
-      uint32_t xy = static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(sl, static_cast<int>(held_xy)));
-      uint32_t b = static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(sl, static_cast<int>(held_b)));
-      if (grab) {
-        SEC(SC_GRAB);
-        if (static_cast<int>(lane) == first) base = atomicAdd(kw.queue, kBatch);
-        base = __builtin_amdgcn_readlane(base, first);
-        // A slot past the image or the queue gets a stream that is never used.
-        // the item split's parameters reloaded from the kernarg segment here (once per 64
-        // items) rather than held in SGPRs across the loop, like the camera (step 1)
-        const KParams kg = kernarg_reload(args, [](const auto& a) { return a.kp; });
-        base += kg.n_static;  // past the waves' first batches
-        q_end = base + kBatch;
-        uint32_t bb, qq, xx, yy;
-        const bool in_image = item_xy(kg, base + lane, bb, qq, xx, yy);
-        held = rng_seed(kg.seed, yy * kg.W + xx, stream_key(bb));
-        held_xy = in_image ? (xx | (yy << 16)) : 0xFFFFFFFFu;
-        held_b = bb;
-        // claims r >= avail take the new batch's slots r - avail (base is a multiple of 64)
-        sl = static_cast<int>(((r - avail) & (kBatch - 1u)) << 2);
-        const Rng st2{static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(sl, static_cast<int>(held.s0))),
-                      static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(sl, static_cast<int>(held.s1))),
-                      static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(sl, static_cast<int>(held.s2))),
-                      static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(sl, static_cast<int>(held.s3)))};
-        const uint32_t xy2 = static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(sl, static_cast<int>(held_xy)));
-        const uint32_t b2 = static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(sl, static_cast<int>(held_b)));
-        if (r >= avail) {
-          st = st2;
-          xy = xy2;
-          b = b2;
+      if constexpr (TABLE) {
+        // The wave reserves the next batch only once the current one is used up: while it
+        // holds fewer items than there are free lanes, the first `avail` of them claim now
+        // and the others in the next iteration, from the new batch. A step then never needs
+        // entries of two batches, so the seeding overwrites the table in place. One wave's
+        // LDS operations stay in order: no barrier between the seeding and the claims' reads.
+        // (A retired lane seeds no entry, so its slot may keep a stale one: the item number,
+        // not the entry, says that the queue has drained.)
+        const bool grab = avail == 0u;
+        unsigned long long mc = m;  // the lanes that claim in this step
+        uint32_t take = n, start = next;
+        if (!grab && n > avail) {
+          mc = m & __builtin_amdgcn_ballot_w64(r < avail);
+          take = avail;
         }
-      }
-      q_next = grab ? base + (n - avail) : next + n;
-      const uint32_t item = r < avail ? next + r : base + (r - avail);
-      if (lane_in(m) && item >= kp.n_items) {
+        if (grab) {
+          SEC(SC_GRAB);
+          wave_lds_order();  // (earlier claims' reads of the old entries)
+          const int first = __ffsll(static_cast<long long>(m)) - 1;
+          uint32_t base = 0;
+          if (static_cast<int>(lane) == first) base = atomicAdd(kw.queue, kBatch);
+          base = __builtin_amdgcn_readlane(base, first);
+          // the item split's parameters reloaded from the kernarg segment here (once per 64
+          // items) rather than held in SGPRs across the loop, like the camera (step 1)
+          const KParams kg = kernarg_reload(args, [](const auto& a) { return a.kp; });
+          base += kg.n_static;  // past the waves' first batches
+          q_end = base + kBatch;
+          seed_entry(kg, base + lane);
+          wave_lds_order();
+          start = base;
+        }
+        q_next = start + take;
+        const uint32_t item = start + r;
+        if (lane_in(mc) && item >= kp.n_items) {
 #ifdef FR_DIAG
-        if (gw < 65536) {
-          const unsigned long long now = __builtin_amdgcn_s_memrealtime();
-          if (now < g_fr_wave_drain[gw]) {
-            g_fr_wave_drain[gw] = now;
-            g_fr_wave_iters[2 * gw] = diag_iter;
+          if (gw < 65536) {
+            const unsigned long long now = __builtin_amdgcn_s_memrealtime();
+            if (now < g_fr_wave_drain[gw]) {
+              g_fr_wave_drain[gw] = now;
+              g_fr_wave_iters[2 * gw] = diag_iter;
+            }
+          }
+#endif
+          active = false;  // queue drained
+          continue;
+        }
+        // the claim is a fetch: no division, multiply or conversion (batch_entry did them)
+        if (lane_in(mc)) {
+          SEC(SC_SETUP);
+          // (a batch starts at a multiple of 64: the item's slot in its batch is item mod 64)
+          const uint32_t ea = lds_addr(lds) + (tid & ~63u) * kBatchEntryBytes + (item & (kBatch - 1u)) * kBatchEntryBytes;
+          const u32x4 e0 = lds_u32x4_at(ea), e1 = lds_u32x4_at(ea + 16u);
+          rng = Rng{e0.x, e0.y, e0.z, e0.w};  // this item's stream: rng_seed(seed, y * W + x, stream_key(b))
+          fx = __uint_as_float(e1.x);
+          fy = __uint_as_float(e1.y);
+          // (an entry past the image edge: s == s_end and no need, as an unsuccessful claim)
+          s = e1.z & 0xFFu;
+          s_end = (e1.z >> 8) & 0xFFu;
+          need = (e1.z >> 16) & 0xFFu;  // NEED_JIT: a sample starts, its jitter and lens sample in step 1
+          // the slot as a register pair {low word, bits 32..}: one shift-and-add forms the
+          // address (through an empty asm: the compiler otherwise shifts the halves apart)
+          uint64_t slot = (static_cast<uint64_t>(e1.z >> 24) << 32) | e1.w;
+#if defined(__HIP_DEVICE_COMPILE__)
+          asm volatile("" : "+v"(slot));
+#endif
+          out = kw.samples + WPS * slot;
+#ifdef FR_DIAG
+          if (s != s_end) {
+            diag_tb = item >> 6;
+            diag_seg0 = nseg;
+          }
+#endif
+        }
+      } else {
+        uint32_t base = 0;
+        const bool grab = n > avail;
+        const int first = __ffsll(static_cast<long long>(m)) - 1;
+        // The item's stream start, pixel and block, by lane permute from the lane that
+        // seeded them: first from the current batch (claims r < avail), then, after a grab,
+        // from the new batch (claims r >= avail). Every lane of the wave is active at both
+        // permutes (a permute reads 0 from an inactive source): a lane retires only after
+        // the queue has drained, and from then on no batch holds a valid item.
+        int sl = static_cast<int>(((next + r) & (kBatch - 1u)) << 2);
+        Rng st{static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(sl, static_cast<int>(held.s0))),
+               static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(sl, static_cast<int>(held.s1))),
+               static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(sl, static_cast<int>(held.s2))),
+               static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(sl, static_cast<int>(held.s3)))};
+        uint32_t xy = static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(sl, static_cast<int>(held_xy)));
+        uint32_t b = static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(sl, static_cast<int>(held_b)));
+        if (grab) {
+          SEC(SC_GRAB);
+          if (static_cast<int>(lane) == first) base = atomicAdd(kw.queue, kBatch);
+          base = __builtin_amdgcn_readlane(base, first);
+          // A slot past the image or the queue gets a stream that is never used.
+          // the item split's parameters reloaded from the kernarg segment here (once per 64
+          // items) rather than held in SGPRs across the loop, like the camera (step 1)
+          const KParams kg = kernarg_reload(args, [](const auto& a) { return a.kp; });
+          base += kg.n_static;  // past the waves' first batches
+          q_end = base + kBatch;
+          uint32_t bb, qq, xx, yy;
+          const bool in_image = item_xy(kg, base + lane, bb, qq, xx, yy);
+          held = rng_seed(kg.seed, yy * kg.W + xx, stream_key(bb));
+          held_xy = in_image ? (xx | (yy << 16)) : 0xFFFFFFFFu;
+          held_b = bb;
+          // claims r >= avail take the new batch's slots r - avail (base is a multiple of 64)
+          sl = static_cast<int>(((r - avail) & (kBatch - 1u)) << 2);
+          const Rng st2{static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(sl, static_cast<int>(held.s0))),
+                        static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(sl, static_cast<int>(held.s1))),
+                        static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(sl, static_cast<int>(held.s2))),
+                        static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(sl, static_cast<int>(held.s3)))};
+          const uint32_t xy2 = static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(sl, static_cast<int>(held_xy)));
+          const uint32_t b2 = static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(sl, static_cast<int>(held_b)));
+          if (r >= avail) {
+            st = st2;
+            xy = xy2;
+            b = b2;
           }
         }
-#endif
-        active = false;  // queue drained
-        continue;
-      }
-      if (lane_in(m)) {
-        SEC(SC_SETUP);
-        const uint32_t x = xy & 0xFFFFu, y = xy >> 16;
-        bool ok = xy != 0xFFFFFFFFu;
-        uint32_t yrow = kp.H - y;  // tracer.rs:171-172: v = ((H - y) + r) / H
-        if (MT) {
-          // render_mt (tracer.rs:86-103): band k from the top is thread t_id = 3 - k;
-          // v = ((t_height - y_band) + r) / H + t_id * 0.25; rows past 4 * t_height unused
-          const uint32_t k = kp.band_h ? y / kp.band_h : 4u;
-          ok = ok && k < 4u;
-          yrow = kp.band_h - (y - k * kp.band_h);
-          vofs = static_cast<float>(3u - k) * 0.25f;
-        }
-        if (ok) {
-          rng = st;  // this item's stream: rng_seed(seed, y * W + x, stream_key(b))
-          // a sub-block k of block b_fine: samples [16 b + 4 k, +4) of the block's slot
-          // (item - k * P in the buffer); a whole block: k = 0
-          const uint32_t k = (b >> 28) & 3u;
-          const bool fine = (b & kFineKey) != 0u;
-          const uint32_t j0 = k * kFineSamples;
-          s = (b & 0x0FFFFFFFu) * kBlockSamples + j0;
-          out = kw.samples + WPS * (static_cast<size_t>(item - k * kp.P) * kp.ks);
+        q_next = grab ? base + (n - avail) : next + n;
+        const uint32_t item = r < avail ? next + r : base + (r - avail);
+        if (lane_in(m) && item >= kp.n_items) {
 #ifdef FR_DIAG
-          diag_tb = item >> 6;
-          diag_seg0 = nseg;
+          if (gw < 65536) {
+            const unsigned long long now = __builtin_amdgcn_s_memrealtime();
+            if (now < g_fr_wave_drain[gw]) {
+              g_fr_wave_drain[gw] = now;
+              g_fr_wave_iters[2 * gw] = diag_iter;
+            }
+          }
 #endif
-          s_end = min(s + (fine ? kFineSamples : kBlockSamples), kp.spp);
-          // 2^24 x + 2^23, exact (x, yrow < 2^23): the jitter's numerator base (step 1)
-          fx = static_cast<float>(x) * 16777216.0f + 8388608.0f;
-          fy = static_cast<float>(yrow) * 16777216.0f + 8388608.0f;
-          need = NEED_JIT;  // a sample starts: its jitter and lens sample in step 1
+          active = false;  // queue drained
+          continue;
+        }
+        if (lane_in(m)) {
+          SEC(SC_SETUP);
+          const uint32_t x = xy & 0xFFFFu, y = xy >> 16;
+          bool ok = xy != 0xFFFFFFFFu;
+          uint32_t yrow = kp.H - y;  // tracer.rs:171-172: v = ((H - y) + r) / H
+          if (MT) {
+            // render_mt (tracer.rs:86-103): band k from the top is thread t_id = 3 - k;
+            // v = ((t_height - y_band) + r) / H + t_id * 0.25; rows past 4 * t_height unused
+            const uint32_t k = kp.band_h ? y / kp.band_h : 4u;
+            ok = ok && k < 4u;
+            yrow = kp.band_h - (y - k * kp.band_h);
+            vofs = static_cast<float>(3u - k) * 0.25f;
+          }
+          if (ok) {
+            rng = st;  // this item's stream: rng_seed(seed, y * W + x, stream_key(b))
+            // a sub-block k of block b_fine: samples [16 b + 4 k, +4) of the block's slot
+            // (item - k * P in the buffer); a whole block: k = 0
+            const uint32_t k = (b >> 28) & 3u;
+            const bool fine = (b & kFineKey) != 0u;
+            const uint32_t j0 = k * kFineSamples;
+            s = (b & 0x0FFFFFFFu) * kBlockSamples + j0;
+            out = kw.samples + WPS * (static_cast<size_t>(item - k * kp.P) * kp.ks);
+#ifdef FR_DIAG
+            diag_tb = item >> 6;
+            diag_seg0 = nseg;
+#endif
+            s_end = min(s + (fine ? kFineSamples : kBlockSamples), kp.spp);
+            // 2^24 x + 2^23, exact (x, yrow < 2^23): the jitter's numerator base (step 1)
+            fx = static_cast<float>(x) * 16777216.0f + 8388608.0f;
+            fy = static_cast<float>(yrow) * 16777216.0f + 8388608.0f;
+            need = NEED_JIT;  // a sample starts: its jitter and lens sample in step 1
+          }
         }
       }
     }
