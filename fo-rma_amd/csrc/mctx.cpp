@@ -91,6 +91,8 @@ int fr_mctx_render(fr_mctx* m, fr_scene* scene, const fr_camera* cam, const fr_p
   m->height = p.height;
   m->t0 = std::chrono::steady_clock::now();
   // enqueue every shard and its gather, then return: the devices run concurrently
+  // (params' flags go to every shard as they are: with FR_FLAG_ACCUMULATE each shard's context
+  // accumulates its own strips)
   for (int i = 0; i < n; ++i) {
     p.shard_index = static_cast<uint32_t>(i);
     if ((rc = fr_ctx_render(m->ctx[i], scene, cam, &p))) return set_error(rc, "shard %d: %s", i, fr_last_error());
@@ -145,9 +147,28 @@ int fr_mctx_download(fr_mctx* m, float* mean_rgb, uint8_t* rgb8) {
   return FR_OK;
 }
 
+int fr_mctx_accum_reset(fr_mctx* m) {
+  if (!m) return set_error(FR_EARG, "fr_mctx_accum_reset: null mctx");
+  for (fr_ctx* c : m->ctx) {
+    const int rc = fr_ctx_accum_reset(c);
+    if (rc) return rc;
+  }
+  return FR_OK;
+}
+
+// Every shard sees the same scene, camera and parameters but its shard index, so all
+// continue or restart together: shard 0's figures are every shard's.
+int fr_mctx_accum_info(fr_mctx* m, uint32_t* frames, uint32_t* samples) {
+  if (!m || m->ctx.empty()) return set_error(FR_EARG, "fr_mctx_accum_info: null mctx");
+  return fr_ctx_accum_info(m->ctx[0], frames, samples);
+}
+
 int fr_render_hip_multi(fr_scene* scene, const fr_camera* cam, const fr_params* params, int n_gpus,
                         float* mean_rgb, uint8_t* rgb8, fr_stats* stats) {
   if (!params || n_gpus < 1) return set_error(FR_EARG, "fr_render_hip_multi: bad arguments");
+  if (params->flags & FR_FLAG_ACCUMULATE)
+    return set_error(FR_EARG,
+                     "fr_render_hip_multi: FR_FLAG_ACCUMULATE needs a context that outlives the call (fr_mctx_render)");
   int avail = 0;
   if (hipGetDeviceCount(&avail) != hipSuccess || avail < n_gpus)
     return set_error(FR_ENODEV, "fr_render_hip_multi: %d devices requested, %d present", n_gpus, avail);

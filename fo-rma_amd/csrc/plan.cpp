@@ -49,6 +49,8 @@ int check_params(const fr_params* p) {
   if (p->strip_rows != kStripRows) return set_error(FR_EARG, "strip_rows must be %u", kStripRows);
   if (p->shard_count == 0 || p->shard_index >= p->shard_count)
     return set_error(FR_EARG, "shard_index %u / shard_count %u invalid", p->shard_index, p->shard_count);
+  if ((p->flags & FR_FLAG_ACCUMULATE) && (p->flags & FR_FLAG_MT_BANDS))
+    return set_error(FR_EARG, "FR_FLAG_ACCUMULATE with FR_FLAG_MT_BANDS: save_image_mt has its own averaging");
   return FR_OK;
 }
 
@@ -103,7 +105,8 @@ int make_plan(const fr_params& p, float cam_reach, const SceneFacts& sf, int num
   kp.seed = p.seed;
   kp.shard_index = p.shard_index;
   kp.shard_count = p.shard_count;
-  kp.flags = p.flags;
+  // (an accumulating frame is planned, traced and cached as the plain frame: the flag stops here)
+  kp.flags = p.flags & ~FR_FLAG_ACCUMULATE;
   kp.tiles_per_row = (p.width + 7u) / 8u;
   kp.band_h = p.height / 4u;
   kp.n_tiles = shard_strips(p.height, p.shard_index, p.shard_count, mt).count * kp.tiles_per_row;
@@ -229,6 +232,35 @@ PassPlan pass_plan(const FramePlan& fp, int pass) {
     pp.n_items = pp.n_coarse + ((n_last + kFineSamples - 1u) / kFineSamples) * kp.P;
   }
   return pp;
+}
+
+AccumKey accum_key(uint64_t scene_uid, const fr_camera& cam, const fr_params& p) {
+  AccumKey k;
+  k.scene_uid = scene_uid;
+  k.cam = cam;
+  k.width = p.width, k.height = p.height, k.max_depth = p.max_depth;
+  k.shard_index = p.shard_index, k.shard_count = p.shard_count;
+  return k;
+}
+
+bool same_view(const AccumKey& a, const AccumKey& b) {
+  return a.scene_uid == b.scene_uid && memcmp(&a.cam, &b.cam, sizeof(fr_camera)) == 0 && a.width == b.width &&
+         a.height == b.height && a.max_depth == b.max_depth && a.shard_index == b.shard_index &&
+         a.shard_count == b.shard_count;
+}
+
+int accum_step(const AccumState& prev, const AccumKey& key, uint32_t spp, AccumStep* out) {
+  AccumStep s;
+  s.start = !(prev.live && same_view(prev.key, key));
+  if (!s.start && spp > 0xFFFFFFFFu - prev.samples)
+    return set_error(FR_EARG, "accumulation of %u samples per pixel cannot take %u more (32-bit count); "
+                     "fr_ctx_accum_reset starts a new one", prev.samples, spp);
+  s.next.live = true;
+  s.next.key = key;
+  s.next.frames = s.start ? 1u : prev.frames + 1u;  // (<= samples while spp >= 1; wraps only with spp 0 frames)
+  s.next.samples = s.start ? spp : prev.samples + spp;
+  *out = s;
+  return FR_OK;
 }
 
 std::string kernel_name(const int t[8]) {

@@ -166,6 +166,41 @@ struct PassPlan {
 };
 PassPlan pass_plan(const FramePlan& fp, int pass);
 
+// ---- progressive accumulation (FR_FLAG_ACCUMULATE) ----------------------------------
+// A context's accumulator A holds the f32 sum of n samples per pixel of one still view; an
+// accumulating frame adds its own per-pixel sum to it and shows A / n (sum.hip's resolve).
+// The flag itself never enters the plan: make_plan drops it from KParams.flags, so an
+// accumulating frame has the plain frame's plan, kernels and scene-kernel cache key.
+
+// What must stay the same from one accumulating frame to the next for A to go on. seed and
+// spp are not part of it: frames of different spp add up, and equal seeds are the caller's
+// business.
+struct AccumKey {
+  uint64_t scene_uid = 0;  // the scene upload's identity: a new one with every edit of the scene
+  fr_camera cam{};         // compared as its 104 bytes
+  uint32_t width = 0, height = 0, max_depth = 0, shard_index = 0, shard_count = 0;
+};
+AccumKey accum_key(uint64_t scene_uid, const fr_camera& cam, const fr_params& p);
+bool same_view(const AccumKey& a, const AccumKey& b);
+
+// A context's accumulation as of its last enqueued accumulating frame.
+struct AccumState {
+  bool live = false;  // false: nothing accumulated yet, or reset (fr_ctx_accum_reset)
+  AccumKey key;
+  uint32_t frames = 0;   // frames in A
+  uint32_t samples = 0;  // n: samples per pixel in A
+};
+
+struct AccumStep {
+  bool start = false;  // A = S; else A = A + S
+  AccumState next;     // the state once this frame is enqueued; next.samples is the divisor n
+};
+
+// The next accumulating frame of `spp` samples seen through `key`: continues `prev` iff prev
+// is live and of the same view, else starts anew. FR_EARG (fr_last_error) when continuing
+// would take n past 2^32 - 1; *out is then untouched.
+int accum_step(const AccumState& prev, const AccumKey& key, uint32_t spp, AccumStep* out);
+
 // ---- kernel choice ----------------------------------------------------------------
 
 template <int KS_, bool HP_, int KREJ_, int MAXD_, bool BV_, bool MT_, int DEFER_, int MAT_ = 0>

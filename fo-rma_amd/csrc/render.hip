@@ -156,6 +156,14 @@ struct fr_ctx {
   float* d_samples = nullptr;
   float* d_running = nullptr;
   size_t cap_mean = 0, cap_u8 = 0, cap_samples = 0, cap_running = 0;  // bytes
+  // Progressive accumulation (FR_FLAG_ACCUMULATE): A, 3 f32 per pixel slot of
+  // the shard like d_running, and the host's record of what it holds as of the last enqueued
+  // accumulating frame (plan.h). Only the last pass's sum of an accumulating frame touches
+  // d_accum, and every sum of the context runs on stream_sum, streamed and pipelined frames
+  // included: the read-modify-writes of consecutive frames are ordered by that stream alone.
+  float* d_accum = nullptr;
+  size_t cap_accum = 0;
+  AccumState accum;
   int num_cus = 0;
   size_t device_bytes = 0;  // HBM size (the sample buffer budget's default)
   fr_params last{};
@@ -215,6 +223,27 @@ static int grow(T*& ptr, size_t& cap, size_t bytes) {
   cap = 0;
   HIPCHK(hipMalloc(&ptr, bytes));
   cap = bytes;
+  return FR_OK;
+}
+
+// The accumulator at `bytes` or more, its contents kept: fr_ctx_prepare may grow it for a
+// larger frame while an accumulation of a smaller one is live. The copy goes on the sum
+// stream, behind every sum that reads or writes the old buffer, which is freed once it is done.
+static int grow_accum(fr_ctx* c, size_t bytes) {
+  if (bytes <= c->cap_accum) return FR_OK;
+  float* bigger = nullptr;
+  HIPCHK(hipMalloc(&bigger, bytes));
+  if (c->d_accum) {
+    hipError_t e = hipMemcpyAsync(bigger, c->d_accum, c->cap_accum, hipMemcpyDeviceToDevice, c->stream_sum);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream_sum);
+    if (e != hipSuccess) {
+      (void)hipFree(bigger);
+      HIPCHK(e);
+    }
+    HIPCHK(hipFree(c->d_accum));
+  }
+  c->d_accum = bigger;
+  c->cap_accum = bytes;
   return FR_OK;
 }
 
@@ -446,7 +475,8 @@ void fr_ctx_free(fr_ctx* c) {
   for (hipStream_t s : {c->stream, c->stream2, c->stream_sum, c->stream_copy})
     if (s) (void)hipStreamSynchronize(s);
   for (void* d : {static_cast<void*>(c->d_mean), static_cast<void*>(c->d_u8), static_cast<void*>(c->d_cnt),
-                  static_cast<void*>(c->d_wcnt), static_cast<void*>(c->d_samples), static_cast<void*>(c->d_running)})
+                  static_cast<void*>(c->d_wcnt), static_cast<void*>(c->d_samples), static_cast<void*>(c->d_running),
+                  static_cast<void*>(c->d_accum)})
     if (d) (void)hipFree(d);
   for (hipEvent_t e : {c->ev0, c->ev1, c->ev_start, c->ev_copy})
     if (e) (void)hipEventDestroy(e);
@@ -472,9 +502,10 @@ int fr_ctx_prepare(fr_ctx* c, fr_scene* scene, const fr_camera* cam, const fr_pa
 }
 
 // Enqueues a planned frame on frame slot fs: the slot's setup, then per pass the trace,
-// the counter reduce and the sum, then the frame's end events.
+// the counter reduce and the sum, then the frame's end events. acc: an accumulating frame's
+// resolve, which its last pass's sum runs (null: a plain frame).
 static int enqueue_frame(fr_ctx* c, const DeviceCopy* dc, const FramePlan& fp, KArgs args, const SceneKernel& sk,
-                         int fs) {
+                         int fs, const SumAccum* acc) {
   unsigned long long* const cnt = c->d_cnt + kCntWords * fs;
   c->t0 = std::chrono::steady_clock::now();
   // The frame's setup (slot wait, counter clear, start events) goes on the stream its trace
@@ -553,7 +584,7 @@ static int enqueue_frame(fr_ctx* c, const DeviceCopy* dc, const FramePlan& fp, K
     const int first = pass == 0, last = pass + 1 >= fp.passes;
     if (first && c->copy_pending) HIPCHK(hipStreamWaitEvent(c->stream_sum, c->ev_copy, 0));  // last gather done
     HIPCHK(launch_sum(fp.wps, sum_blocks ? sum_blocks : 1u, c->stream_sum, kp, samples, c->d_running,
-                      c->d_mean, c->d_u8, first, last, sum_att, sum_n));
+                      c->d_mean, c->d_u8, first, last, sum_att, sum_n, acc));
     HIPCHK(hipEventRecord(c->ev_sum[pass], c->stream_sum));
     summed = pass + 1;
     if (last) break;
@@ -607,6 +638,16 @@ static int render_impl(fr_ctx* c, fr_scene* scene, const fr_camera* cam, const f
   const int fs = fp.fpipe ? c->frame_slot % fp.nfs : 0;
   if ((rc = grow(c->d_samples, c->cap_samples, fp.slot_bytes * fp.slots))) return rc;
   if (fp.passes > 1 && (rc = grow(c->d_running, c->cap_running, fp.running_bytes))) return rc;
+  // an accumulating frame (the flag is not in the plan: plan.h): continue or restart is
+  // decided, and may fail, before anything is enqueued; the state moves once the frame is
+  const bool accumulate = (p->flags & FR_FLAG_ACCUMULATE) != 0;
+  AccumStep step;
+  SumAccum acc;
+  if (accumulate) {
+    if ((rc = grow_accum(c, fp.running_bytes ? fp.running_bytes : 1u))) return rc;
+    if (!dry && (rc = accum_step(c->accum, accum_key(dc->uid, *cam, *p), p->spp, &step))) return rc;
+    acc = SumAccum{c->d_accum, step.start, static_cast<float>(step.next.samples)};
+  }
   const size_t n_ev = static_cast<size_t>(fp.passes > 0 ? fp.passes : 1);
   if ((rc = grow_events(c->ev_sum, n_ev, hipEventDisableTiming))) return rc;
   if ((rc = grow_events(c->ev_trace, 2 * n_ev, hipEventDefault))) return rc;
@@ -617,7 +658,10 @@ static int render_impl(fr_ctx* c, fr_scene* scene, const fr_camera* cam, const f
   if (dry) {
     c->jit_used = sk.fn != nullptr;
   } else {
-    if ((rc = enqueue_frame(c, dc, fp, KArgs{kscene(dc, fp), kcam(cam), fp.kp, kw}, sk, fs))) return rc;
+    if ((rc = enqueue_frame(c, dc, fp, KArgs{kscene(dc, fp), kcam(cam), fp.kp, kw}, sk, fs,
+                            accumulate ? &acc : nullptr)))
+      return rc;
+    if (accumulate) c->accum = step.next;
     c->last = *p;
     c->last_n = dc->ps.facts.n;
     c->pending = true;
@@ -806,6 +850,9 @@ int fr_ctx_device_buffers(fr_ctx* c, float** d_mean, uint8_t** d_u8) {
 
 int fr_render_hip(fr_scene* scene, const fr_camera* cam, const fr_params* params, int device, float* mean_rgb,
                   uint8_t* rgb8, fr_stats* stats) {
+  if (params && (params->flags & FR_FLAG_ACCUMULATE))
+    return set_error(FR_EARG,
+                     "fr_render_hip: FR_FLAG_ACCUMULATE needs a context that outlives the call (fr_ctx_render)");
   fr_ctx* c = nullptr;
   int rc = fr_ctx_create(device, nullptr, &c);
   if (rc) return rc;
@@ -846,6 +893,19 @@ int fr_ctx_jit_state(fr_ctx* c, int* state) {
 }
 
 int fr_jit_wait(void) { return jit_wait_all(); }
+
+int fr_ctx_accum_reset(fr_ctx* c) {
+  if (!c) return set_error(FR_EARG, "fr_ctx_accum_reset: null ctx");
+  c->accum = AccumState{};  // (host state only: the next accumulating frame's sum overwrites A)
+  return FR_OK;
+}
+
+int fr_ctx_accum_info(fr_ctx* c, uint32_t* frames, uint32_t* samples) {
+  if (!c) return set_error(FR_EARG, "fr_ctx_accum_info: null ctx");
+  if (frames) *frames = c->accum.live ? c->accum.frames : 0u;
+  if (samples) *samples = c->accum.live ? c->accum.samples : 0u;
+  return FR_OK;
+}
 
 int fr_ctx_trace_log(fr_ctx* c, int enable) {
   if (!c) return set_error(FR_EARG, "fr_ctx_trace_log: null ctx");

@@ -11,9 +11,19 @@ namespace fr {
 
 constexpr uint32_t kSumThreads = 256;
 
+// An accumulating frame's resolve (FR_FLAG_ACCUMULATE): launch arguments of the accumulating
+// sum kernels, which only a frame's last pass runs.
+struct SumAccum {
+  float* accum = nullptr;  // A: 3 f32 per pixel slot of the shard, indexed like `running`
+  bool start = false;      // A = S (a new accumulation), else A = A + S
+  float divisor = 1.0f;    // (float)n, the samples per pixel A holds after this frame
+};
+
 // wps: words per sample record (2 or 3); the record's form by KParams flags.
+// acc: null for a plain frame; otherwise the last pass adds the frame's sum to acc->accum and
+// writes accum / divisor instead of sum / spp.
 hipError_t launch_sum(uint32_t wps, uint32_t blocks, hipStream_t stream, const KParams& kp,
                       const float* samples, float* running, float* out_mean, uint8_t* out_u8, int first, int last,
-                      const float4* att, uint32_t n_prims);
+                      const float4* att, uint32_t n_prims, const SumAccum* acc = nullptr);
 
 }  // namespace fr

@@ -24,11 +24,35 @@ static_assert(kSumThreads % 64u == 0 && kSumThreads <= kDeferUnit + 1u, "whole w
 // whose 56 VGPRs per wave leave 512 - 7 x 56 = 120 per SIMD lane for one sum wave
 constexpr int kSumVgprs = 120;
 #define FR_SUM_VGPR_CAP __attribute__((amdgpu_num_vgpr(kSumVgprs)))
-template <uint32_t WPS>
+
+// The resolve step of an accumulating frame (FR_FLAG_ACCUMULATE), in the
+// last pass only and after the block loop, so the accumulator's three loads are issued when
+// the sample registers are dead and do not raise the peak. `sum` is the frame's own sum S,
+// its spp samples added in sample order from zero; it enters the accumulator as a unit:
+// A = S (start) or A = A + S, one f32 add per channel, then mean = A / divisor with divisor =
+// (float)n, the samples per pixel A then holds (IEEE division, as the plain frame's S / spp).
+// A is indexed like `running`: 3 f32 per pixel slot of the shard. Plain f32 without
+// compensation: it stops improving in the region of 2^24 samples per pixel.
+__device__ __forceinline__ V3 accum_resolve(uint32_t q, V3 sum, float* __restrict__ accum, int start, float divisor) {
+  V3 a = sum;
+  if (!start) a = add(V3{accum[3 * q], accum[3 * q + 1], accum[3 * q + 2]}, sum);
+  accum[3 * q] = a.x;
+  accum[3 * q + 1] = a.y;
+  accum[3 * q + 2] = a.z;
+  return divs(a, divisor);
+}
+
+// ACC: empty for the plain kernels, which take the arguments they always took and compile to
+// the same code; {float* accum, int start, float divisor} for the accumulating variant
+// (launch_sum). They are arguments of the accumulating kernels alone, not KParams members:
+// KParams is shared with the trace kernel and the scene-kernel cache key.
+template <uint32_t WPS, class... ACC>
 __global__ __launch_bounds__(kSumThreads) FR_SUM_VGPR_CAP void sum_kernel(KParams kp, const float* __restrict__ samples,
                                                           float* __restrict__ running, float* __restrict__ out_mean,
                                                           uint8_t* __restrict__ out_u8, int first, int last,
-                                                          const float4* __restrict__ att, uint32_t n_prims) {
+                                                          const float4* __restrict__ att, uint32_t n_prims,
+                                                          ACC... acc) {
+  constexpr bool kAcc = sizeof...(ACC) != 0;
   constexpr uint32_t kSumSlot = WPS * kBlockSamples + 1;  // floats per slot in LDS (odd stride)
   // one LDS block, the attenuation table first: its entries then sit at LDS byte offset
   // 12 x index, and the per-level reads need no base-address add (the table behind the
@@ -59,7 +83,7 @@ __global__ __launch_bounds__(kSumThreads) FR_SUM_VGPR_CAP void sum_kernel(KParam
   const uint32_t nq = min(kSumThreads, kp.P - q0);
   uint32_t x = 0, y = 0;
   const bool valid = q < kp.P && slot_xy(kp, q, x, y);
-  const bool mt = (kp.flags & FR_FLAG_MT_BANDS) != 0;
+  const bool mt = !kAcc && (kp.flags & FR_FLAG_MT_BANDS) != 0;  // (save_image_mt never accumulates: FR_EARG)
   const bool mt_zero = mt && !(kp.band_h && y / kp.band_h < 4u);  // rows render_mt never fills stay 0
   V3 sum = (first || !valid) ? V3{0.0f, 0.0f, 0.0f} : V3{running[3 * q], running[3 * q + 1], running[3 * q + 2]};
   // The running sum's loads land here, before the first block's loads are issued. Left to
@@ -179,7 +203,11 @@ __global__ __launch_bounds__(kSumThreads) FR_SUM_VGPR_CAP void sum_kernel(KParam
     out_u8[idx + 2] = as_u8_trunc(sum.z);
     return;
   }
-  const V3 mean = divs(sum, static_cast<float>(kp.spp));  // tracer.rs:177
+  V3 mean;
+  if constexpr (kAcc)
+    mean = accum_resolve(q, sum, acc...);
+  else
+    mean = divs(sum, static_cast<float>(kp.spp));  // tracer.rs:177
   out_mean[idx + 0] = mean.x;
   out_mean[idx + 1] = mean.y;
   out_mean[idx + 2] = mean.z;
@@ -196,9 +224,12 @@ __global__ __launch_bounds__(kSumThreads) FR_SUM_VGPR_CAP void sum_kernel(KParam
 // next frame's trace this kernel runs one wave per SIMD: the tile's 64 LDS writes and reads
 // per thread and block, and its two barriers per block, were what it waited on there.
 // Same sums in the same order as sum_kernel<2>, which takes the other 8-B-record launches.
+template <class... ACC>
 __global__ __launch_bounds__(kSumThreads) FR_SUM_VGPR_CAP void sum_nib_kernel(
     KParams kp, const float* __restrict__ samples, float* __restrict__ running, float* __restrict__ out_mean,
-    uint8_t* __restrict__ out_u8, int first, int last, const float4* __restrict__ att, uint32_t n_prims) {
+    uint8_t* __restrict__ out_u8, int first, int last, const float4* __restrict__ att, uint32_t n_prims,
+    ACC... acc) {
+  constexpr bool kAcc = sizeof...(ACC) != 0;
   __shared__ float4 att16[16];  // level k's entry at byte 16 x nibble (15: the unit entry)
   const uint32_t t = threadIdx.x;
   if (t < 16u) {
@@ -263,7 +294,11 @@ __global__ __launch_bounds__(kSumThreads) FR_SUM_VGPR_CAP void sum_nib_kernel(
     return;
   }
   const size_t idx = (static_cast<size_t>(y) * kp.W + x) * 3u;
-  const V3 mean = divs(sum, static_cast<float>(kp.spp));  // tracer.rs:177
+  V3 mean;
+  if constexpr (kAcc)
+    mean = accum_resolve(q, sum, acc...);
+  else
+    mean = divs(sum, static_cast<float>(kp.spp));  // tracer.rs:177
   out_mean[idx + 0] = mean.x;
   out_mean[idx + 1] = mean.y;
   out_mean[idx + 2] = mean.z;
@@ -276,10 +311,23 @@ __global__ __launch_bounds__(kSumThreads) FR_SUM_VGPR_CAP void sum_nib_kernel(
 
 hipError_t launch_sum(uint32_t wps, uint32_t blocks, hipStream_t stream, const KParams& kp,
                       const float* samples, float* running, float* out_mean, uint8_t* out_u8, int first, int last,
-                      const float4* att, uint32_t n_prims) {
+                      const float4* att, uint32_t n_prims, const SumAccum* acc) {
   const dim3 grid(blocks), block(kSumThreads);
-  if (wps == 2 && kp.ks == kBlockSamples && !(kp.flags & FR_FLAG_MT_BANDS))
-    hipLaunchKernelGGL(sum_nib_kernel, grid, block, 0, stream, kp, samples, running, out_mean, out_u8, first, last,
+  const bool nib = wps == 2 && kp.ks == kBlockSamples && !(kp.flags & FR_FLAG_MT_BANDS);
+  if (acc && last) {  // only a frame's last pass resolves; earlier passes run the plain kernels
+    if (!acc->accum || (kp.flags & FR_FLAG_MT_BANDS)) return hipErrorInvalidValue;
+    const int start = acc->start ? 1 : 0;
+    if (nib)
+      hipLaunchKernelGGL((sum_nib_kernel<float*, int, float>), grid, block, 0, stream, kp, samples, running, out_mean,
+                         out_u8, first, last, att, n_prims, acc->accum, start, acc->divisor);
+    else if (wps == 2)
+      hipLaunchKernelGGL((sum_kernel<2, float*, int, float>), grid, block, 0, stream, kp, samples, running, out_mean,
+                         out_u8, first, last, att, n_prims, acc->accum, start, acc->divisor);
+    else
+      hipLaunchKernelGGL((sum_kernel<3, float*, int, float>), grid, block, 0, stream, kp, samples, running, out_mean,
+                         out_u8, first, last, att, n_prims, acc->accum, start, acc->divisor);
+  } else if (nib)
+    hipLaunchKernelGGL((sum_nib_kernel<>), grid, block, 0, stream, kp, samples, running, out_mean, out_u8, first, last,
                        att, n_prims);
   else if (wps == 2)
     hipLaunchKernelGGL((sum_kernel<2>), grid, block, 0, stream, kp, samples, running, out_mean, out_u8, first,

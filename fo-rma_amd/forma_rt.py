@@ -36,6 +36,7 @@ FR_FLAG_MT_BANDS = 2  # save_image_mt semantics (forma_rt.h)
 FR_FLAG_SCENE_JIT = 4  # scene-specialised trace kernel (hiprtc, cached; same image bits)
 FR_FLAG_SCENE_JIT_WAIT = 8  # ... compiled on the render's thread when missing (else in the background)
 FR_FLAG_SCENE_JIT_CACHED = 16  # ... only when already built or on disk; never compiled (one-shot callers)
+FR_FLAG_ACCUMULATE = 32  # the frame's sum joins the context's accumulator; outputs show the running mean
 FR_JIT_OFF, FR_JIT_USED, FR_JIT_PENDING, FR_JIT_FAILED, FR_JIT_MISS = 0, 1, 2, 3, 4  # fr_ctx_jit_state
 MAX_DEPTH = 50  # tracer.rs:10
 DEFAULT_SEED = 0x5EED
@@ -93,6 +94,7 @@ EXPORTS = (
     "fr_selftest_div",
     "fr_post_process", "fr_post_process_device", "fr_rgb_to_rgba_device", "fr_ctx_jit_info", "fr_selftest_jit",
     "fr_ctx_prepare", "fr_ctx_jit_state", "fr_jit_wait",
+    "fr_ctx_accum_reset", "fr_ctx_accum_info", "fr_mctx_accum_reset", "fr_mctx_accum_info",
 )
 
 _lib = None
@@ -185,6 +187,11 @@ def lib():
         L.fr_ctx_jit_state.argtypes = [vp, P(C.c_int)]
         L.fr_jit_wait.argtypes = []
         L.fr_selftest_jit.argtypes = [C.c_char_p, P(C.c_uint32), C.c_uint32, P(C.c_int), P(C.c_size_t), P(C.c_double)]
+    if hasattr(L, "fr_ctx_accum_info"):  # absent from A/B builds of older sources
+        L.fr_ctx_accum_reset.argtypes = [vp]
+        L.fr_ctx_accum_info.argtypes = [vp, P(C.c_uint32), P(C.c_uint32)]
+        L.fr_mctx_accum_reset.argtypes = [vp]
+        L.fr_mctx_accum_info.argtypes = [vp, P(C.c_uint32), P(C.c_uint32)]
     _lib = L
     return L
 
@@ -406,16 +413,18 @@ def scene_path(name):
 # ---- rendering ----------------------------------------------------------------
 
 def make_params(width, height, spp, max_depth=MAX_DEPTH, seed=DEFAULT_SEED, shard_index=0, shard_count=1,
-                write_u8=True, mt_bands=False, scene_jit=False):
+                write_u8=True, mt_bands=False, scene_jit=False, accumulate=False):
     """scene_jit: False, True (the scene kernel once it is compiled; until then renders run
     the compiled-in kernel, same bits), "wait" (compile on the render's thread if needed) or
-    "cached" (the scene kernel only if already built or on disk; never a compile)."""
+    "cached" (the scene kernel only if already built or on disk; never a compile).
+    accumulate: FR_FLAG_ACCUMULATE, the frame refines the context's accumulation of this view
+    (forma_rt.h); give every frame its own seed."""
     p = FrParams()
     p.width, p.height, p.spp, p.max_depth, p.seed = width, height, spp, max_depth, seed
     p.strip_rows, p.shard_index, p.shard_count = 8, shard_index, shard_count
     p.flags = ((FR_FLAG_WRITE_U8 if write_u8 else 0) | (FR_FLAG_MT_BANDS if mt_bands else 0) |
                (FR_FLAG_SCENE_JIT if scene_jit else 0) | (FR_FLAG_SCENE_JIT_WAIT if scene_jit == "wait" else 0) |
-               (FR_FLAG_SCENE_JIT_CACHED if scene_jit == "cached" else 0))
+               (FR_FLAG_SCENE_JIT_CACHED if scene_jit == "cached" else 0) | (FR_FLAG_ACCUMULATE if accumulate else 0))
     return p
 
 
@@ -527,6 +536,17 @@ class RenderContext:
         check(lib().fr_ctx_jit_info(self._h, C.byref(used), C.byref(ms), C.byref(comp)))
         return {"used": bool(used.value), "ms": ms.value, "compiled": bool(comp.value), "state": self.jit_state()}
 
+    def accum_reset(self):
+        """The next accumulating frame (make_params(accumulate=True)) starts a new accumulation."""
+        check(lib().fr_ctx_accum_reset(self._h))
+
+    def accum_info(self):
+        """(frames, samples per pixel) in the accumulator as of the last enqueued frame; (0, 0)
+        when there is none. No sync."""
+        frames, samples = C.c_uint32(0), C.c_uint32(0)
+        check(lib().fr_ctx_accum_info(self._h, C.byref(frames), C.byref(samples)))
+        return frames.value, samples.value
+
     def jit_state(self):
         """FR_JIT_OFF / USED / PENDING / FAILED for the last render (fr_ctx_jit_state)."""
         s = C.c_int(0)
@@ -608,6 +628,16 @@ class MultiContext:
         fp, up = C.POINTER(C.c_float)(), C.POINTER(C.c_uint8)()
         check(lib().fr_mctx_frame(self._h, C.byref(fp), C.byref(up)))
         return C.cast(fp, C.c_void_p).value, C.cast(up, C.c_void_p).value
+
+    def accum_reset(self):
+        """Every shard's next accumulating frame starts a new accumulation."""
+        check(lib().fr_mctx_accum_reset(self._h))
+
+    def accum_info(self):
+        """(frames, samples per pixel) accumulated: shard 0's figures, which every shard shares."""
+        frames, samples = C.c_uint32(0), C.c_uint32(0)
+        check(lib().fr_mctx_accum_info(self._h, C.byref(frames), C.byref(samples)))
+        return frames.value, samples.value
 
     def context(self, i):
         """The i-th shard's RenderContext view (not owned: do not close it)."""
@@ -702,14 +732,16 @@ class TraceModel:
         mean, u8 = ctx.download(self.width, self.height)
         return mean, u8, self.last_stats
 
-    def frame_u8(self, scene, max_depth, seed):
+    def frame_u8(self, scene, max_depth, seed, accumulate=False):
         """update()'s frame: 1 spp, only the u8 image copied back, by DMA into page-locked
         memory that `pixels` views (overwritten by the next frame, as tracer.rs's
         model.pixels is). The view keeps the page-locked block alive, so an array returned
         here stays valid memory after the model is closed or collected; copy it to keep a
-        frame past the next update()."""
+        frame past the next update(). accumulate: the frame joins the context's accumulation
+        (FR_FLAG_ACCUMULATE) and the image is the mean of every frame in it."""
         ctx = self.context()
-        ctx.render(scene, self.scene.camera, make_params(self.width, self.height, 1, max_depth, seed))
+        ctx.render(scene, self.scene.camera, make_params(self.width, self.height, 1, max_depth, seed,
+                                                         accumulate=accumulate))
         self.last_stats = ctx.sync()
         if self._pinned is None:
             self._pinned = PinnedFrame(self.width, self.height)
@@ -737,15 +769,17 @@ def create_model(width, height, scene=None):
     return TraceModel(scene, width, height)
 
 
-def update(model, keys, delta_time, max_depth=MAX_DEPTH):
+def update(model, keys, delta_time, max_depth=MAX_DEPTH, accumulate=False):
     """tracer.rs:30-55: key bitmask 00EQADWS -> camera.orbit(delta), then one 1-spp frame
-    into model.pixels. Each frame draws from its own RNG key."""
+    into model.pixels. Each frame draws from its own RNG key. accumulate: while no key is
+    pressed the frames add up on the model's context and model.pixels converges (the mean of
+    every frame since the camera last moved); a key press moves the camera, which starts anew."""
     d = (C.c_float * 3)()
     check(lib().fr_update_delta(int(keys) & 0xFF, float(delta_time), d))
     camera_orbit(model.scene.camera, list(d))
     seed = model.seed ^ (0x9E3779B97F4A7C15 * (model.frame + 1) & 0xFFFFFFFFFFFFFFFF)
     model.frame += 1
-    return model.frame_u8(model.scene, max_depth, seed)
+    return model.frame_u8(model.scene, max_depth, seed, accumulate=accumulate)
 
 
 def write_png(path, rgb8):

@@ -56,7 +56,9 @@ extern "C" {
                                entry points restore the caller's current HIP device
                             5: FR_FLAG_SCENE_JIT, fr_ctx_prepare, fr_ctx_jit_info
                             6: FR_FLAG_SCENE_JIT compiles in the background (renders never wait),
-                               FR_FLAG_SCENE_JIT_WAIT, fr_ctx_jit_state, fr_jit_wait */
+                               FR_FLAG_SCENE_JIT_WAIT, fr_ctx_jit_state, fr_jit_wait
+                               (still 6, additive: FR_FLAG_ACCUMULATE, fr_ctx_accum_reset / _info,
+                               fr_mctx_accum_reset / _info) */
 
 /* error codes */
 #define FR_OK 0
@@ -104,6 +106,21 @@ extern "C" {
    one-shot callers: a queued background compile runs to its end when the process exits, so
    a process that renders once and exits would otherwise wait for hiprtc at exit. */
 #define FR_FLAG_SCENE_JIT_CACHED 16u
+/* Progressive accumulation: the frame is traced exactly like the plain frame (same kernels,
+   records and counters), but its per-pixel sum S (its spp samples added in sample order from
+   zero) is added to the context's accumulator A (3 f32 per pixel of the shard) and the
+   outputs show the running mean: A = S when the frame starts an accumulation, else A = A + S
+   (one f32 add per channel); n += spp; mean = A / (float)n; u8 from that mean. The first frame
+   of an accumulation is bit-identical to the plain render. A frame continues the context's
+   accumulation iff the scene (as uploaded: any edit counts), the 104 bytes of the camera,
+   width, height, max_depth, shard_index and shard_count equal the previous accumulating
+   frame's; otherwise, and after fr_ctx_accum_reset, it starts a new one. seed and spp may
+   differ from frame to frame (give every frame its own seed). Plain renders on the same
+   context in between neither read nor disturb A and n. A is plain f32 without compensation:
+   it stops improving in the region of 2^24 samples per pixel; a frame that would take n past
+   2^32 - 1 is FR_EARG. FR_EARG with FR_FLAG_MT_BANDS (save_image_mt has its own averaging)
+   and through fr_render_hip / fr_render_hip_multi (their context dies with the call). */
+#define FR_FLAG_ACCUMULATE 32u
 /* fr_ctx_jit_state: which trace kernel the last render (or fr_ctx_prepare) ran */
 #define FR_JIT_OFF 0     /* compiled-in kernel: not asked for, a BVH scene, or > 64 primitives */
 #define FR_JIT_USED 1    /* the scene-specialised kernel */
@@ -251,6 +268,11 @@ int fr_ctx_jit_info(fr_ctx* ctx, int* used, double* ms, int* compiled);
 int fr_ctx_jit_state(fr_ctx* ctx, int* state);
 /* Block until no scene-kernel compile is queued or running in this process. */
 int fr_jit_wait(void);
+/* FR_FLAG_ACCUMULATE: the next accumulating frame starts a new accumulation. */
+int fr_ctx_accum_reset(fr_ctx* ctx);
+/* Frames and samples per pixel in the accumulator (0, 0 when there is none). Host-side, as of
+   the last enqueued frame; no sync. Either may be NULL. */
+int fr_ctx_accum_info(fr_ctx* ctx, uint32_t* frames, uint32_t* samples);
 
 /* ---- persistent multi-device context (tracer.rs:83-134 render_mt, one device per shard) ----
    Entry i of `devices` renders row shard i of n of every frame on its own fr_ctx (device
@@ -271,6 +293,10 @@ int fr_mctx_sync(fr_mctx* mctx, fr_stats* stats);
 int fr_mctx_frame(fr_mctx* mctx, const float** mean_rgb, const uint8_t** rgb8);
 /* Wait, then copy the host frame into caller buffers (either may be NULL). */
 int fr_mctx_download(fr_mctx* mctx, float* mean_rgb, uint8_t* rgb8);
+/* FR_FLAG_ACCUMULATE passes through fr_mctx_render to every shard's context; these reset every
+   shard's accumulation and report shard 0's figures (all shards agree by construction). */
+int fr_mctx_accum_reset(fr_mctx* mctx);
+int fr_mctx_accum_info(fr_mctx* mctx, uint32_t* frames, uint32_t* samples);
 
 /* Page-locked host memory (hipHostMalloc) for fr_ctx_download_async targets. */
 int fr_host_alloc(size_t bytes, void** out);

@@ -2,10 +2,13 @@
 simple scene (get_simple_scene, max_depth 50) with an orbiting camera, on the model's
 persistent render context, including the u8 download into model.pixels.
 
-    python tools/time_update.py [W H] [frames]
+    python tools/time_update.py [W H] [frames] [--accumulate]
 
 Prints one JSON line: median / p90 host wall time per update() call, and the same frame
-through the one-shot fr_render_hip (a context made and freed per call) for comparison."""
+through the one-shot fr_render_hip (a context made and freed per call) for comparison.
+--accumulate: the timed calls are update(..., accumulate=True) with no key pressed, so the
+camera stands still and every frame continues the accumulation (the resolve's read and write
+of the accumulator); "accum_frames" then says how many frames the last picture holds."""
 import json
 import os
 import sys
@@ -17,16 +20,24 @@ import forma_rt as fr  # noqa: E402
 
 
 def main():
-    w, h = (int(sys.argv[1]), int(sys.argv[2])) if len(sys.argv) > 2 else (1920, 1080)
-    frames = int(sys.argv[3]) if len(sys.argv) > 3 else 30
+    argv = [a for a in sys.argv[1:] if a != "--accumulate"]
+    accumulate = len(argv) != len(sys.argv) - 1
+    w, h = (int(argv[0]), int(argv[1])) if len(argv) > 1 else (1920, 1080)
+    frames = int(argv[2]) if len(argv) > 2 else 30
     m = fr.create_model(w, h)
     fr.update(m, 0b001000, 1.0 / 60)  # first frame: context, scene upload, buffers
+    if accumulate:
+        fr.update(m, 0, 1.0 / 60, accumulate=True)  # the accumulator's allocation
     ts = []
     for k in range(frames):
         t = time.perf_counter()
-        fr.update(m, 0b001000 if k % 2 else 0b000100, 1.0 / 60)
+        if accumulate:
+            fr.update(m, 0, 1.0 / 60, accumulate=True)
+        else:
+            fr.update(m, 0b001000 if k % 2 else 0b000100, 1.0 / 60)
         ts.append((time.perf_counter() - t) * 1e3)
     st = m.last_stats
+    accum_frames = m.ctx.accum_info()[0] if accumulate else 0
     one = []
     for _ in range(5):
         t = time.perf_counter()
@@ -35,6 +46,7 @@ def main():
     ts.sort()
     one.sort()
     print(json.dumps({"workload": f"update() simple scene {w}x{h} 1spp depth 50", "frames": frames,
+                      "accumulate": accumulate, "accum_frames": accum_frames,
                       "ms_median": round(ts[len(ts) // 2], 3), "ms_p90": round(ts[int(0.9 * len(ts))], 3),
                       "kernel_ms": round(st["kernel_ms"], 3), "fps_median": round(1e3 / ts[len(ts) // 2], 1),
                       "one_shot_render_ms_median": round(one[len(one) // 2], 3),
