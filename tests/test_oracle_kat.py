@@ -178,6 +178,130 @@ def test_triangle_list_order_and_ties():
     assert O.closest_hit([a, a], (0, 0, 0), (0, 0, -1))[0] == 0
 
 
+# ---- edge rays: exact zeros and on-surface origins -------------------
+# The single-ray definitions behind tests/test_ray_edges.py, on the lattice its scenes use.
+
+def _box(lo, hi):
+    return S.prim(S.AABB, 0, (1, 1, 1), 0.0, list(lo) + list(hi))
+
+
+P100 = f32(2.0) ** 100  # the clamp of the box's reciprocal direction
+
+
+def test_box_face_grazing_ray_hits_only_with_the_zero_pointing_inward():
+    """An origin in a face plane with d_k = 0: inv_k = +-2^100, so the face's own distance is
+    fma(c, inv, -c inv) = 0 and the other face's +-2^101. The x slab is [0, 2^101] when the
+    zero points into the box (+0 in the low face, -0 in the high face) and [-2^101, 0]
+    otherwise, which leaves tf = 0: a miss. The hit enters through z: normal axis z, sign +."""
+    left, right = _box((-1, -1, -6), (1, 1, -4)), _box((1, -1, -6), (3, 1, -4))
+    for box, plane_x, inward in ((left, -1.0, 0.0), (left, 1.0, -0.0), (right, 1.0, 0.0), (right, 3.0, -0.0)):
+        best, rec = O.closest_hit([box], (plane_x, 0.5, 0), (inward, 0, -1))
+        assert best == 0 and rec[0] == 4.0 and list(rec[1:4]) == [plane_x, 0.5, -4.0] and list(rec[4:]) == [0, 0, 1.0]
+        assert O.closest_hit([box], (plane_x, 0.5, 0), (-inward, 0, -1))[0] == -1
+    # in the plane two boxes share, +0 takes the box on the high side and -0 the one on the low side
+    assert O.closest_hit([left, right], (1.0, 0.5, 0), (0.0, 0, -1))[0] == 1
+    assert O.closest_hit([left, right], (1.0, 0.5, 0), (-0.0, 0, -1))[0] == 0
+
+
+def test_box_origin_on_a_shared_face_takes_the_neighbours_far_root():
+    a, b = _box((-1, -1, -1), (1, 1, 1)), _box((1, -1, -1), (3, 1, 1))
+    best, rec = O.closest_hit([a, b], (1.0, 0, 0), (1, 0, 0))
+    # a: slab [-2, 0], no root above t_min; b: tn = 0 is not above t_min either, so its far root
+    assert best == 1 and rec[0] == 2.0 and list(rec[1:4]) == [3.0, 0, 0] and list(rec[4:]) == [1.0, 0, 0]
+    best, rec = O.closest_hit([a, b], (1.0, 0, 0), (-1, 0, 0))
+    assert best == 0 and rec[0] == 2.0 and list(rec[4:]) == [-1.0, 0, 0]
+
+
+def test_box_zero_direction_exits_at_2_pow_100_with_sign_zero_negative():
+    """d = 0 inside a box: every far distance is 2^100 (hi - o) for +0 and 2^100 (o - lo) for
+    -0; the least one wins, p == o, and the exit normal +sign(d_k) counts sign(0) as negative:
+    -1 on the winning axis, whichever face that is."""
+    box = _box((-1, -1, -5), (1, 1, -3))
+    o = (0.25, 0.5, -4.25)
+    best, rec = O.closest_hit([box], o, (0.0, 0.0, 0.0))
+    assert best == 0 and rec[0] == f32(0.5) * P100 and list(rec[1:4]) == list(o) and list(rec[4:]) == [0, -1.0, 0]
+    best, rec = O.closest_hit([box], o, (-0.0, -0.0, -0.0))
+    assert best == 0 and rec[0] == f32(0.75) * P100 and list(rec[1:4]) == list(o) and list(rec[4:]) == [0, 0, -1.0]
+    # outside, just below the low z face: entered at 2^100 (lo - o), entry normal -sign(0) = +1;
+    # further below than the x and y exits are away, or above the high face: no root
+    best, rec = O.closest_hit([box], (0.0, 0.0, -5.25), (0.0, 0.0, 0.0))
+    assert best == 0 and rec[0] == f32(0.25) * P100 and list(rec[4:]) == [0, 0, 1.0]
+    assert O.closest_hit([box], (0.25, 0.5, -6.5), (0.0, 0.0, 0.0))[0] == -1
+    assert O.closest_hit([box], (0.25, 0.5, 0.0), (0.0, 0.0, 0.0))[0] == -1
+
+
+def test_obb_face_grazing_ray_misses():
+    """The oriented box keeps (lo - o) * (1 / d): in a face plane that is 0 * inf = NaN, which
+    minNum / maxNum ignore, leaving near = far = +-inf on that axis: a miss for either zero."""
+    obb = S.prim(S.OBB, 0, (1, 1, 1), 0.0, [0, 0, -5, 1, 0, 0, 0, 1, 0, 0, 0, 1, 1, 1, 1])
+    for x in (-1.0, 1.0):
+        for z in (0.0, -0.0):
+            assert O.closest_hit([obb], (x, 0.5, 0), (z, 0, -1))[0] == -1
+    assert O.closest_hit([obb], (0.5, 0.5, 0), (0.0, 0, -1))[0] == 0  # d_k = 0 off the face planes hits
+    assert O.closest_hit([obb], (0.25, 0.5, -5.25), (0.0, 0.0, 0.0))[0] == -1  # d = 0: tf = inf is no root
+
+
+def _quad(cx, cy, cz):
+    v00, v10, v11, v01 = (cx - 1, cy - 1, cz), (cx + 1, cy - 1, cz), (cx + 1, cy + 1, cz), (cx - 1, cy + 1, cz)
+    return [_tri(v00, v10, v11), _tri(v11, v01, v00)]
+
+
+def test_triangle_edges_are_inclusive_and_the_first_listed_wins():
+    q = _quad(0.0, 0.0, -4.0)
+    # on the shared diagonal u == 0 in both triangles: both hit at t = 4, the first listed wins
+    for order in (q, q[::-1]):
+        best, rec = O.closest_hit(order, (0.5, 0.5, 0), (0, 0, -1))
+        assert best == 0 and rec[0] == 4.0
+    assert O.closest_hit([q[1]], (0.5, 0.5, 0), (0, 0, -1))[0] == 0
+    # the edge x = 1 is v1-v2 (u + v == 1) of the first triangle here and of the neighbour's second
+    r = _quad(2.0, 0.0, -4.0)
+    assert O.closest_hit([q[0]], (1.0, 0.5, 0), (0, 0, -1))[0] == 0
+    assert O.closest_hit([r[1]], (1.0, 0.5, 0), (0, 0, -1))[0] == 0
+    assert O.closest_hit(q + r, (1.0, 0.5, 0), (0.0, 0, -1))[0] == 0
+    assert O.closest_hit(r + q, (1.0, 0.5, 0), (-0.0, 0, -1))[0] == 1  # r[0] does not hold the edge
+    # an origin on a vertex or an edge: t = 0 is below t_min; det == 0 (d in the plane, d = 0): NaN fails
+    assert O.closest_hit(q, (1.0, 1.0, -4.0), (0.25, 0.5, -1))[0] == -1
+    assert O.closest_hit(q, (0.0, -1.0, -4.0), (1, 0, 0))[0] == -1
+    assert O.closest_hit(q, (0.25, 0.5, 0), (0.0, 0.0, 0.0))[0] == -1
+
+
+def test_plane_rim_misses_and_leaves_a_stale_t():
+    tile = S.plane((0.0, 0.0, -4.0), (0.0, 0.0, -1.0), (1.0, 1.0, 1.0), 0, (1, 1, 1), 0.0)
+    best, rec = O.closest_hit([tile], (1.0, 0.5, 0), (0, 0, -1))  # p.x == position.x + size.x: strict
+    assert best == -1 and rec[0] == 4.0 and list(rec[1:4]) == [1.0, 0.5, -4.0]
+    assert O.closest_hit([tile], (0.5, -1.0, 0), (0, 0, -1))[0] == -1
+    assert O.closest_hit([tile], (0.5, 0.5, 0), (0.0, -0.0, -1))[0] == 0
+    assert O.closest_hit([tile], (0.5, 0.5, 0), (0.0, 0.0, 0.0))[0] == -1  # denom = 0 is not above t_min
+
+
+def test_plane_listed_after_a_nearer_winner_replaces_it():
+    """plane.rs:26 gates on t_min < dot(orientation, d) < closest, not on t: a plane behind
+    the winner still wins when its denominator is below the winner's t."""
+    box = _box((-1, -1, -5), (1, 1, -3))
+    back = S.plane((0.0, 0.0, -16.0), (0.0, 0.0, -1.0), (16.0, 16.0, 1.0), 0, (1, 1, 1), 0.0)
+    best, rec = O.closest_hit([box, back], (0.5, 0.5, 0), (0, 0, -1))
+    assert best == 1 and rec[0] == 16.0
+    best, rec = O.closest_hit([back, box], (0.5, 0.5, 0), (0, 0, -1))
+    assert best == 1 and rec[0] == 3.0
+
+
+def test_sphere_zero_discriminant_and_zero_direction_miss():
+    a, b = _sphere((0.0, 0.0, -4.0), 1.0), _sphere((2.0, 0.0, -4.0), 1.0)
+    # through the point where the two spheres touch: disc == 0 for both (strict, sphere.rs:30)
+    assert O.closest_hit([a, b], (1.0, 0.0, 0), (0.0, 0, -1))[0] == -1
+    assert O.closest_hit([a, b], (1.0, 0.0, 0), (-0.0, 0.5, -1))[0] == -1
+    # a == 0: disc = b b - 0 c = 0, from the centre, the surface and outside
+    for o in ((0.0, 0.0, -4.0), (0.0, 0.0, -3.0), (0.25, 0.5, 0.0)):
+        assert O.closest_hit([a], o, (0.0, 0.0, 0.0))[0] == -1
+    # from the centre both roots are +-r / |d|: the far one, outward normal
+    best, rec = O.closest_hit([a], (0.0, 0.0, -4.0), (0.0, 0, -2))
+    assert best == 0 and rec[0] == 0.5 and list(rec[4:]) == [0, 0, -1.0]
+    # from the pole, tangent: b == 0 and c == 0, disc == 0; inward: the far root
+    assert O.closest_hit([a], (0.0, 0.0, -3.0), (1, 0, 0.0))[0] == -1
+    best, rec = O.closest_hit([a], (0.0, 0.0, -3.0), (0.0, 0, -1))
+    assert best == 0 and rec[0] == 2.0
+
+
 def test_camera_new_basis():
     # camera.rs:24-60 at 2:1 aspect: w = +z, u = +x, v = +y, tan(30deg) half height
     c = O.camera_to_array(O.camera_new(200, 100))
