@@ -14,6 +14,8 @@
 #include <stdint.h>
 
 #if !defined(__HIPCC_RTC__)  // the constants below are also read by the run-time kernel build
+#include <math.h>
+
 #include <vector>
 
 #include "../../include/forma_rt.h"
@@ -77,15 +79,48 @@ bool build_segments(const std::vector<fr_prim>& prims, std::vector<BvhSegment>& 
                     std::vector<uint32_t>& order, bool force = false, float* extent = nullptr);
 #endif
 
-// Ray origins the node cull is conservative for: |o| <= kBvhOriginReach * (extent + 1)
-// (the kernel's fused node slabs add |o| 2^-24 to a slab distance; the padding allows
-// 2^24 * 1e-4 = 1677 times that). A camera farther out renders with the in-order loop.
+// Ray origins the node cull's slab arithmetic is conservative for:
+// |o| <= kBvhOriginReach * (extent + 1) (the kernel's fused node slabs add |o| 2^-24 to a
+// slab distance; the padding allows 2^24 * 1e-4 = 1677 times that). The reach of a scene is
+// bvh_origin_reach below, which is shorter with spheres; a camera farther out renders with
+// the in-order loop, and so does a wave with a scatter origin farther out.
 constexpr float kBvhOriginReach = 100.0f;
 // The node cull's reciprocal direction is clamped to [-kBvhInvClamp, kBvhInvClamp]: a
 // zero direction component (inv = +-inf) would make fma(lo, inv, -o inv) NaN. A clamped
-// slab is still conservative: a hit inside a box padded by >= 1e-4 keeps that axis's
-// slab >= 1e-4 * 2^100 ~ 1e26 wide, and |o| 2^100 stays finite.
+// slab is conservative while the hit's t is far below its width: a hit inside a box padded by
+// >= 1e-4 (extent + 1) keeps that axis's slab >= 1e-4 (extent + 1) 2^100 wide about the
+// origin, and a direction with one component of 2^-70 or more has every hit at
+// t <= 101 (extent + 1) 2^70. A direction that is tiny in every component (hits at
+// t ~ 2^100, clamped or not) takes the in-order loop: kBvhTinyDir, the kernel's list_walk
+// ballot, which also sends an overflowing o inv (|o| >= 2^28 with a clamped component) there.
 constexpr float kBvhInvClamp = 0x1p100f;
+constexpr float kBvhTinyDir = 0x1p-70f;
+
+#if !defined(__HIPCC_RTC__)
+// The reach for a scene: kBvhOriginReach extents, less for a scene with spheres. The sphere
+// test's discriminant b b - a c carries a rounding error of up to 15 * 2^-24 |o - c|^2 a
+// (three-term dot products, the two products and the difference), so from far away it accepts
+// rays that pass the sphere at a distance of up to sqrt(r^2 + E) with
+// E = 2^-20 |o - c|^2, and the cull must not reject what the test accepts. Half of the padding
+// covers that for |o - c|^2 <= 3 (|o| + extent)^2 while E <= r pad + pad^2 / 4, r the
+// smallest radius. The reach is never set below extent + 1, because every scatter origin
+// lies there and a shorter reach would switch the BVH off: that floor is a policy, not a
+// bound. Where extent is more than about 10 r (the test lattices; 10,000 spheres of radius
+// 2.5 over +-5000) the derived distance is below the floor, and inside the floor the test can
+// still accept a far sphere by rounding error that the cull rejects. No frame of the suite
+// shows it (such a far "hit" lies behind nearer ones almost always); closing it needs sphere
+// bounds padded by the test's own error, which is not done here.
+inline float bvh_origin_reach(float extent, float sphere_rmin) {
+  const float unit = extent + 1.0f;
+  float reach = kBvhOriginReach * unit;
+  if (sphere_rmin >= 0.0f) {
+    const float pad = 1e-4f * extent + 1e-4f;
+    const float safe = sqrtf((sphere_rmin * pad + 0.25f * pad * pad) * (1048576.0f / 3.0f)) - extent;
+    reach = fminf(reach, fmaxf(unit, safe));
+  }
+  return reach;
+}
+#endif
 
 #if !defined(__HIPCC_RTC__)
 // Largest internal-node depth of the trees (root = 0): below kBvhStack by construction.

@@ -88,8 +88,8 @@ int make_plan(const fr_params& p, float cam_reach, const SceneFacts& sf, int num
               const PlanEnv& env, bool dry, const PlanHistory& hist, FramePlan* out) {
   FramePlan fp;
   const bool mt = (p.flags & FR_FLAG_MT_BANDS) != 0;
-  // the node cull holds for origins within kBvhOriginReach scene extents (bvh.h)
-  const bool cam_near = cam_reach <= kBvhOriginReach * (sf.bvh_extent + 1.0f);
+  // the node cull holds for origins within the scene's reach (bvh.h bvh_origin_reach)
+  const bool cam_near = cam_reach <= bvh_origin_reach(sf.bvh_extent, sf.bvh_sphere_rmin);
   // save_image_mt renders run the in-order list kernels (select_kernel), whose LDS layout
   // (sample staging, no traversal stack) the size below must follow
   fp.use_bvh = sf.bvh_ok && sf.n_segs > 0 && cam_near && !env.bvh_off && !mt;

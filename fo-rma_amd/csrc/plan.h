@@ -88,6 +88,7 @@ struct SceneFacts {
   // lane at depth d holds at most d entries and writes the free one): the BVH launch's LDS
   uint32_t bvh_levels = kBvhStack;
   float bvh_extent = 0;  // largest |coordinate| of the primitives' bounds (bvh.h)
+  float bvh_sphere_rmin = -1.0f;  // the smallest sphere's radius (-1: no sphere): bvh_origin_reach
   bool diffuse = true;   // no metal or dielectric scatter class (trace_kernel MAT = 1)
   // attenuation classes: the scene's distinct attenuations (bit patterns), when there are at
   // most kNibbleMaxPrims of them (else 0): BVH kernels with 8-B records store a path's

@@ -390,7 +390,7 @@ static KScene kscene(const DeviceCopy* dc, const FramePlan& fp) {
   ks.runs = reinterpret_cast<const uint4*>(b + ps.off_runs);
   ks.n_runs = ps.n_runs;
   ks.n_segs = fp.use_bvh ? ps.facts.n_segs : 0u;
-  ks.reach = kBvhOriginReach * (ps.facts.bvh_extent + 1.0f);
+  ks.reach = bvh_origin_reach(ps.facts.bvh_extent, ps.facts.bvh_sphere_rmin);
   ks.att_nonneg = ps.att_nonneg ? 1u : 0u;
   return ks;
 }

@@ -902,14 +902,23 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(FR_NUM_SGPR)
       const SphereSeg ssg = sphere_seg(a_dd);  // unused (removed) in kernels without spheres
       float closest = FLT_MAX, t_last = 0.0f;
       int best = -1;
-      // The node cull is conservative only for origins within kBvhOriginReach scene
-      // extents (bvh.h). A stale plane record (plane.rs:27-40) can put a scatter origin
-      // p = o + t_stale d far outside: a wave holding such a lane (or a NaN origin) tests
-      // the list in order instead, which the BVH walk equals bit for bit.
+      // The node cull is conservative only under three conditions (bvh.h); a wave holding a
+      // lane outside any of them tests the list in order instead, which the BVH walk equals
+      // bit for bit:
+      //  - the origin within the scene's reach (sc.reach = bvh_origin_reach: up to
+      //    kBvhOriginReach extents, less with spheres). A stale plane record (plane.rs:27-40)
+      //    can put a scatter origin p = o + t_stale d far outside; a NaN origin fails too.
+      //  - a direction component of kBvhTinyDir or more: with every component tiny the hits
+      //    lie at t ~ 2^100, where neither the padding's allowance nor the clamped reciprocal
+      //    (below) holds.
+      //  - o inv finite: |o| 2^100 overflows from |o| = 2^28, and fma(lo, inv, -inf) puts both
+      //    planes of a slab the origin is inside at -inf.
       bool list_walk = !BVH;
       if (BVH) {
         const float ao = fmax3_num(__builtin_fabsf(o.x), __builtin_fabsf(o.y), __builtin_fabsf(o.z));
-        list_walk = __ballot(!(ao <= sc.reach)) != 0;
+        const float ad = fmax3_num(__builtin_fabsf(d.x), __builtin_fabsf(d.y), __builtin_fabsf(d.z));
+        const float aoi = fmax3_num(__builtin_fabsf(boinv.x), __builtin_fabsf(boinv.y), __builtin_fabsf(boinv.z));
+        list_walk = __ballot(!(ao <= sc.reach) | !(ad >= kBvhTinyDir) | !(aoi <= FLT_MAX)) != 0;
       }
       if (BVH && !list_walk) {
         // The list cut at its planes (bvh.h), walked in list order: each plane tested
@@ -943,13 +952,16 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(FR_NUM_SGPR)
           // write cost an address add.)
           uint32_t tso = tbase + 4u * tid;
           // node slabs as fma(lo, inv, -o inv): a cull only, covered by the padding for
-          // origins within kBvhOriginReach scene extents (bvh.h; the host checks the camera).
+          // origins within the scene's reach (bvh.h bvh_origin_reach; the host checks the camera,
+          // the ballot above every segment's origin).
           // The cull's reciprocal is clamped to +-2^100 (bvh.h kBvhInvClamp): an exact-zero
           // direction component (a lambertian bounce ((p + n) + r) - p at |p| ~ 5000 gives one
           // every few thousand scatters) has inv = +-inf, and fma(lo, inf, -(o inf)) is
           // inf - inf = NaN, which culled boxes the ray is inside. With the clamp, o inv is
           // finite and a slab that holds the ray's hit by the padding (>= 1e-4) stays
-          // >= 1e-4 * 2^100 wide on that axis.
+          // >= 1e-4 * 2^100 wide on that axis. (Today `inv` arrives clamped: a lane with
+          // recip_box_ok has |inv| <= 2^100 and a wave without one clamps every lane above, so
+          // the fmed3 changes no value; it keeps the cull right if that fallback ever changes.)
           const V3 invc{__builtin_amdgcn_fmed3f(inv.x, -kBvhInvClamp, kBvhInvClamp),
                         __builtin_amdgcn_fmed3f(inv.y, -kBvhInvClamp, kBvhInvClamp),
                         __builtin_amdgcn_fmed3f(inv.z, -kBvhInvClamp, kBvhInvClamp)};

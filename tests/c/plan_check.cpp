@@ -4,8 +4,8 @@
 //
 //   plan_check plan KEY=VALUE...   one frame plan: the render parameters (w h spp depth
 //                                  shard=i/n flags seed), the scene's facts (n kinds
-//                                  has_plane bvh_ok n_segs bvh_levels bvh_extent diffuse
-//                                  n_aclass), the device (cus device_gib), the camera's reach
+//                                  has_plane bvh_ok n_segs bvh_levels bvh_extent bvh_sphere_rmin
+//                                  diffuse n_aclass), the device (cus device_gib), the camera's reach
 //                                  and the context's history (prev_in_flight streaming fs_n
 //                                  fs_bytes dry); the knobs come from the environment
 //   plan_check kernels             every specialisation select_kernel can reach, once each
@@ -61,6 +61,7 @@ static int do_plan(int argc, char** argv) {
   sf.n_segs = u32("n_segs", sf.bvh_ok ? 1 : 0);
   sf.bvh_levels = u32("bvh_levels", fr::kBvhStack);
   sf.bvh_extent = static_cast<float>(num("bvh_extent", 10.0));
+  sf.bvh_sphere_rmin = static_cast<float>(num("bvh_sphere_rmin", -1.0));
   sf.diffuse = u32("diffuse", 1) != 0;
   sf.n_aclass = u32("n_aclass", 0);
   fr::PlanHistory hist;

@@ -357,3 +357,81 @@ def test_oracle_rng_matches_restatement(seed, pixel, sample):
     x, b = _splitmix(x)
     want = _xoshiro([a & 0xFFFFFFFF, a >> 32, b & 0xFFFFFFFF, b >> 32], 64)
     assert list(O.rng_stream(seed, pixel, sample, 64)) == want
+
+
+# ---- magnitude edges: tiny, huge and denormal directions ----------------
+# The single-ray definitions behind tests/test_magnitude.py.
+
+def _p2(k):
+    return f32(np.ldexp(1.0, k))
+
+
+def test_box_tiny_direction_component_uses_the_clamped_reciprocal():
+    """d_k = 2^-110 has 1 / d_k = 2^110, clamped to 2^100: the slab distances of that axis are
+    2^100 (c - o), not 2^110 (c - o). Seen from x = 1.5 with d = (-2^-110, 0, -2^-100) the box's
+    x slab is [0.5, 2.5] 2^100 and its z slab [1, 3] 2^100: entered through z at t = 2^100. With
+    the unclamped reciprocal the x slab would start at 0.5 * 2^110: a miss."""
+    box = _box((-1, -4, -3), (1, 4, -1))
+    best, rec = O.closest_hit([box], (1.5, 0, 0), (-_p2(-110), 0.0, -_p2(-100)))
+    assert best == 0 and rec[0] == P100 and list(rec[4:]) == [0, 0, 1.0]
+    assert list(rec[1:4]) == [f32(1.5) - _p2(-10), 0.0, -1.0]  # p = o + t d with the true d
+    # at unit scale the tiny component only decides which side of a face plane the ray is on
+    unit = _box((-1, -1, -6), (1, 1, -4))
+    assert O.closest_hit([unit], (0.0, 0.5, 0), (_p2(-110), 0, -1))[1][0] == 4.0
+    assert O.closest_hit([unit], (1.0, 0.5, 0), (-_p2(-110), 0, -1))[0] == 0   # in the face plane, inward
+    assert O.closest_hit([unit], (1.0, 0.5, 0), (_p2(-110), 0, -1))[0] == -1   # outward: slab [-2^101, 0]
+
+
+def test_box_denormal_direction_component_is_clamped_like_a_zero():
+    """1 / 2^-149 overflows to inf and is clamped to 2^100 with its sign, as 1 / +-0 is."""
+    unit = _box((-1, -1, -6), (1, 1, -4))
+    for tiny in (_p2(-149), _p2(-127)):
+        best, rec = O.closest_hit([unit], (-1.0, 0.5, 0), (tiny, 0, -1))
+        assert best == 0 and rec[0] == 4.0 and list(rec[4:]) == [0, 0, 1.0]
+        assert O.closest_hit([unit], (-1.0, 0.5, 0), (-tiny, 0, -1))[0] == -1
+    obb = S.prim(S.OBB, 0, (1, 1, 1), 0.0, [0, 0, -5, 1, 0, 0, 0, 1, 0, 0, 0, 1, 1, 1, 1])
+    # the oriented box keeps 1 / d: inf off a face plane is a slab of [-inf, inf], a hit
+    assert O.closest_hit([obb], (0.5, 0.5, 0), (_p2(-149), 0, -1))[0] == 0
+    assert O.closest_hit([obb], (1.0, 0.5, 0), (-_p2(-149), 0, -1))[0] == -1  # 0 inf = NaN in the face plane
+
+
+def test_sphere_with_a_underflowing_to_zero_misses():
+    """d = (0, 0, -2^-75): a = 2^-150 rounds to 0 while b b = 25 * 2^-150 rounds to 12 * 2^-149, so
+    disc > 0 and both roots are a positive numerator over 0 = +inf, which is not below t_max."""
+    s = _sphere((0.0, 0.0, -5.0), 1.0)
+    assert O.vec3(2, (0, 0, -_p2(-75)), (0, 0, -_p2(-75)))[0] == 0.0
+    assert O.closest_hit([s], (0, 0, 0), (0, 0, -_p2(-75)))[0] == -1
+    # one binade up a is the least denormal and the near root 4 / 2^-74 is found
+    best, rec = O.closest_hit([s], (0, 0, 0), (0, 0, -_p2(-74)))
+    assert best == 0 and list(rec[1:4]) == [0, 0, -4.0]
+
+
+def test_sphere_with_an_infinite_discriminant_misses():
+    """|oc| = 5, r = 4.8, d = (0, 0, -2^63): b b = 25 * 2^126 overflows while a c = 1.96 * 2^126
+    does not, disc = inf, and the roots are (-b -+ inf) / a = -+inf: a miss, although the ray
+    points at the sphere."""
+    s = _sphere((0.0, 0.0, -5.0), 4.8)
+    assert O.closest_hit([s], (0, 0, 0), (0, 0, -_p2(63)))[0] == -1
+    assert O.closest_hit([s], (0, 0, 0), (0, 0, -1.0))[0] == 0
+
+
+def _sky(d):
+    """The sky colour of direction d: one sample of an empty scene."""
+    cam = O.OrCamera()
+    for k in range(3):
+        cam.lower_left[k] = float(f32(d[k]))
+    cam.aspect, cam.focus_dist = 1.0, 1.0
+    mean, _, cnt, _ = O.render([], cam, 1, 1, 1, 8, seed=1)
+    assert cnt["segments"] == 1 and cnt["hits"] == 0
+    return mean[0, 0]
+
+
+def test_sky_of_overflowing_and_denormal_directions():
+    up, mid = [f32(0.5), f32(0.7), f32(1.0)], [f32(0.75), f32(0.85), f32(1.0)]
+    assert list(_sky((0, 3.0, 4.0))) == list((f32(1.0) - f32(0.8)) * f32(1.0) + f32(0.8) * np.asarray(up, dtype=f32))
+    # dot(d, d) = inf: unit(d) = d / inf = 0 and the blend parameter is 0.5 whatever d.y is
+    assert list(_sky((0, _p2(64), _p2(64)))) == mid and list(_sky((0, -_p2(64), 0))) == mid
+    # dot(d, d) = 2^-140 is a denormal whose root 2^-70 is exact: straight up
+    assert list(_sky((0, _p2(-70), 0))) == up
+    # dot(d, d) underflows to 0: d.y / 0 = inf, and (1 - inf) + inf 0.5 is NaN
+    assert np.isnan(_sky((0, _p2(-80), 0))).all()

@@ -29,61 +29,15 @@ import pytest
 
 from oracle import oracle_py as O
 from tests import ray_edge_fixtures as X
-from tests.test_gpu_parity import _same_bits, assert_parity
-from tests.test_scene_jit import _ctx_render
+from tests.parity_runs import Runs
 
 pytestmark = pytest.mark.gpu
-ENV = ("FR_DEFER", "FR_MAT", "FR_BVH")
-
-
-class _Runs:
-    """Renders of one fixture; every mismatch is collected, so one failing case shows every
-    kernel family that deviates."""
-
-    def __init__(self, gpu, monkeypatch, kind, size, name):
-        self.gpu, self.mp, self.key, self.errors = gpu, monkeypatch, (kind, size, name), []
-        self.cam = X.cameras(gpu, X.fixture(kind, name))[0]
-
-    def render(self, prims, depth, env=None, jit=False):
-        for e in ENV:
-            self.mp.delenv(e, raising=False)
-        if env:
-            self.mp.setenv(*env)
-        sc = self.gpu.Scene.from_prims(prims)  # a fresh scene: FR_BVH acts when the scene is uploaded
-        if jit:
-            mean, u8, st, info = _ctx_render(self.gpu, sc, self.cam, X.W, X.H, X.SPP, depth, seed=X.SEED)
-            if not info["used"]:
-                self.errors.append(f"scene kernel not used: {info}")
-            return mean, u8, st
-        return self.gpu.render(sc, self.cam, X.W, X.H, X.SPP, depth, seed=X.SEED)
-
-    def check(self, tag, got, want):
-        mean, u8, st = got
-        omean, ou8, ocnt = want
-        try:
-            if not np.isnan(omean).any():
-                assert_parity(mean, u8, st, omean, ou8, ocnt)
-            assert _same_bits(mean, omean), f"mean bits differ in {int((mean.view(np.uint32) != omean.view(np.uint32)).any(axis=2).sum())} pixels"
-            assert np.array_equal(u8, ou8), "u8 differs"
-            for k in ("segments", "hits", "scatters"):
-                assert st[k] == ocnt[k], f"{k}: {st[k]} != {ocnt[k]}"
-        except AssertionError as e:
-            self.errors.append(f"{tag}: {str(e).splitlines()[0] if str(e) else 'assertion failed'}")
-
-    def against_oracle(self, variant, depth, env=None, jit=False):
-        kind, size, name = self.key
-        prims, omean, ou8, ocnt = X.reference(self.gpu, kind, size, variant, name, depth)
-        got = self.render(prims, depth, env, jit)
-        self.check(f"{variant} depth {depth} {env or ''}{' scene kernel' if jit else ''}", got, (omean, ou8, ocnt))
-        return got
-
-    def done(self):
-        assert not self.errors, f"{self.key}:\n  " + "\n  ".join(self.errors)
 
 
 @pytest.mark.parametrize("kind,size,name", X.cases())
 def test_edge_rays_match_the_oracle(gpu, kind, size, name, monkeypatch):
-    r = _Runs(gpu, monkeypatch, kind, size, name)
+    r = Runs(gpu, monkeypatch, (kind, size, name), X.cameras(gpu, X.fixture(kind, name))[0],
+             lambda variant, depth: X.reference(gpu, kind, size, variant, name, depth), (X.W, X.H, X.SPP, X.SEED))
     if size == "big":
         prims = X.lattice(kind, size, X.fixture(kind, name).shift)
         assert X.bvh_cost(prims) >= 48 and len(prims) >= 48  # so the product takes the BVH path
