@@ -163,6 +163,27 @@ int fr_mctx_accum_info(fr_mctx* m, uint32_t* frames, uint32_t* samples) {
   return fr_ctx_accum_info(m->ctx[0], frames, samples);
 }
 
+// Every shard's estimate (fr_ctx_accum_error): counts add, the maximum is the shards' maximum,
+// and each shard's rows of the map land in `rel`.
+int fr_mctx_accum_error(fr_mctx* m, float threshold, fr_accum_error* out, float* rel) {
+  if (!m || m->ctx.empty() || !out) return set_error(FR_EARG, "fr_mctx_accum_error: null argument");
+  fr_accum_error agg;
+  memset(&agg, 0, sizeof(agg));
+  for (size_t i = 0; i < m->ctx.size(); ++i) {
+    fr_accum_error e;
+    int rc = fr_ctx_accum_error(m->ctx[i], threshold, &e);
+    if (!rc && rel) rc = fr_ctx_download_error(m->ctx[i], rel);
+    if (rc) return set_error(rc, "shard %zu: %s", i, std::string(fr_last_error()).c_str());
+    if (i == 0) agg.frames = e.frames, agg.samples = e.samples;
+    agg.pixels += e.pixels;
+    agg.converged += e.converged;
+    agg.max_rel = std::max(agg.max_rel, e.max_rel);  // (rel is never NaN)
+  }
+  agg.threshold = threshold;
+  *out = agg;
+  return FR_OK;
+}
+
 int fr_render_hip_multi(fr_scene* scene, const fr_camera* cam, const fr_params* params, int n_gpus,
                         float* mean_rgb, uint8_t* rgb8, fr_stats* stats) {
   if (!params || n_gpus < 1) return set_error(FR_EARG, "fr_render_hip_multi: bad arguments");

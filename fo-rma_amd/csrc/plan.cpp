@@ -51,6 +51,10 @@ int check_params(const fr_params* p) {
     return set_error(FR_EARG, "shard_index %u / shard_count %u invalid", p->shard_index, p->shard_count);
   if ((p->flags & FR_FLAG_ACCUMULATE) && (p->flags & FR_FLAG_MT_BANDS))
     return set_error(FR_EARG, "FR_FLAG_ACCUMULATE with FR_FLAG_MT_BANDS: save_image_mt has its own averaging");
+  if ((p->flags & FR_FLAG_ACCUM_ERROR) && !(p->flags & FR_FLAG_ACCUMULATE))
+    return set_error(FR_EARG, "FR_FLAG_ACCUM_ERROR without FR_FLAG_ACCUMULATE: the error estimate is an accumulation's");
+  if ((p->flags & FR_FLAG_ACCUM_ERROR) && p->spp == 0)
+    return set_error(FR_EARG, "FR_FLAG_ACCUM_ERROR with spp 0: a frame without samples has no S^2 / spp");
   return FR_OK;
 }
 
@@ -106,7 +110,7 @@ int make_plan(const fr_params& p, float cam_reach, const SceneFacts& sf, int num
   kp.shard_index = p.shard_index;
   kp.shard_count = p.shard_count;
   // (an accumulating frame is planned, traced and cached as the plain frame: the flag stops here)
-  kp.flags = p.flags & ~FR_FLAG_ACCUMULATE;
+  kp.flags = p.flags & ~(FR_FLAG_ACCUMULATE | FR_FLAG_ACCUM_ERROR);
   kp.tiles_per_row = (p.width + 7u) / 8u;
   kp.band_h = p.height / 4u;
   kp.n_tiles = shard_strips(p.height, p.shard_index, p.shard_count, mt).count * kp.tiles_per_row;
@@ -240,13 +244,14 @@ AccumKey accum_key(uint64_t scene_uid, const fr_camera& cam, const fr_params& p)
   k.cam = cam;
   k.width = p.width, k.height = p.height, k.max_depth = p.max_depth;
   k.shard_index = p.shard_index, k.shard_count = p.shard_count;
+  k.error = (p.flags & FR_FLAG_ACCUM_ERROR) ? 1u : 0u;
   return k;
 }
 
 bool same_view(const AccumKey& a, const AccumKey& b) {
   return a.scene_uid == b.scene_uid && memcmp(&a.cam, &b.cam, sizeof(fr_camera)) == 0 && a.width == b.width &&
          a.height == b.height && a.max_depth == b.max_depth && a.shard_index == b.shard_index &&
-         a.shard_count == b.shard_count;
+         a.shard_count == b.shard_count && a.error == b.error;
 }
 
 int accum_step(const AccumState& prev, const AccumKey& key, uint32_t spp, AccumStep* out) {
@@ -259,6 +264,7 @@ int accum_step(const AccumState& prev, const AccumKey& key, uint32_t spp, AccumS
   s.next.key = key;
   s.next.frames = s.start ? 1u : prev.frames + 1u;  // (<= samples while spp >= 1; wraps only with spp 0 frames)
   s.next.samples = s.start ? spp : prev.samples + spp;
+  s.next.has_q = key.error != 0;
   *out = s;
   return FR_OK;
 }

@@ -172,6 +172,7 @@ PassPlan pass_plan(const FramePlan& fp, int pass);
 // accumulating frame adds its own per-pixel sum to it and shows A / n (sum.hip's resolve).
 // The flag itself never enters the plan: make_plan drops it from KParams.flags, so an
 // accumulating frame has the plain frame's plan, kernels and scene-kernel cache key.
+// FR_FLAG_ACCUM_ERROR (a second accumulator Q of S^2 / spp) is dropped with it.
 
 // What must stay the same from one accumulating frame to the next for A to go on. seed and
 // spp are not part of it: frames of different spp add up, and equal seeds are the caller's
@@ -180,6 +181,9 @@ struct AccumKey {
   uint64_t scene_uid = 0;  // the scene upload's identity: a new one with every edit of the scene
   fr_camera cam{};         // compared as its 104 bytes
   uint32_t width = 0, height = 0, max_depth = 0, shard_index = 0, shard_count = 0;
+  // the frame's FR_FLAG_ACCUM_ERROR bit (0 or 1): Q describes an accumulation only if every
+  // frame of it added to Q, so a frame whose bit differs starts a new accumulation
+  uint32_t error = 0;
 };
 AccumKey accum_key(uint64_t scene_uid, const fr_camera& cam, const fr_params& p);
 bool same_view(const AccumKey& a, const AccumKey& b);
@@ -190,6 +194,7 @@ struct AccumState {
   AccumKey key;
   uint32_t frames = 0;   // frames in A
   uint32_t samples = 0;  // n: samples per pixel in A
+  bool has_q = false;    // the accumulation carries Q (every frame of it had FR_FLAG_ACCUM_ERROR)
 };
 
 struct AccumStep {

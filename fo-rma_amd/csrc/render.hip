@@ -26,6 +26,7 @@
 #include <cmath>
 #include <string>
 
+#include "accum_error.h"
 #include "hipchk.h"
 #include "jit.h"
 #include "pack.h"
@@ -40,6 +41,7 @@ static_assert(sizeof(fr_prim) == 88, "fr_prim layout");
 static_assert(sizeof(fr_camera) == 104, "fr_camera layout");
 static_assert(sizeof(fr_params) == 40, "fr_params layout");
 static_assert(sizeof(fr_stats) == 72, "fr_stats layout");
+static_assert(sizeof(fr_accum_error) == 32, "fr_accum_error layout");
 
 struct DeviceCopy {
   int device = -1;
@@ -164,6 +166,21 @@ struct fr_ctx {
   float* d_accum = nullptr;
   size_t cap_accum = 0;
   AccumState accum;
+  // FR_FLAG_ACCUM_ERROR: Q, the second-moment accumulator, exists once a frame
+  // asked for it and then has A's size, lifetime and ordering (the sum stream alone). accum_kp:
+  // the last accumulating frame's constants, which map A's and Q's pixel slots to the image
+  // for the error kernel (a plain render in between changes `last`, not these).
+  float* d_sq = nullptr;
+  size_t cap_sq = 0;
+  KParams accum_kp{};
+  // fr_ctx_accum_error's outputs: the W x H map of rel, the per-workgroup partials and the
+  // summary; err_kp: the frame constants the map was written with (fr_ctx_download_error)
+  float* d_err = nullptr;
+  uint32_t* d_err_part = nullptr;
+  ErrSummary* d_err_sum = nullptr;
+  size_t cap_err = 0, cap_err_part = 0;
+  KParams err_kp{};
+  bool err_valid = false;
   int num_cus = 0;
   size_t device_bytes = 0;  // HBM size (the sample buffer budget's default)
   fr_params last{};
@@ -226,25 +243,33 @@ static int grow(T*& ptr, size_t& cap, size_t bytes) {
   return FR_OK;
 }
 
-// The accumulator at `bytes` or more, its contents kept: fr_ctx_prepare may grow it for a
-// larger frame while an accumulation of a smaller one is live. The copy goes on the sum
+// An accumulator (A or Q) at `bytes` or more, its contents kept: fr_ctx_prepare may grow it for
+// a larger frame while an accumulation of a smaller one is live. The copy goes on the sum
 // stream, behind every sum that reads or writes the old buffer, which is freed once it is done.
-static int grow_accum(fr_ctx* c, size_t bytes) {
-  if (bytes <= c->cap_accum) return FR_OK;
+static int grow_kept(fr_ctx* c, float*& buf, size_t& cap, size_t bytes) {
+  if (bytes <= cap) return FR_OK;
   float* bigger = nullptr;
   HIPCHK(hipMalloc(&bigger, bytes));
-  if (c->d_accum) {
-    hipError_t e = hipMemcpyAsync(bigger, c->d_accum, c->cap_accum, hipMemcpyDeviceToDevice, c->stream_sum);
+  if (buf) {
+    hipError_t e = hipMemcpyAsync(bigger, buf, cap, hipMemcpyDeviceToDevice, c->stream_sum);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream_sum);
     if (e != hipSuccess) {
       (void)hipFree(bigger);
       HIPCHK(e);
     }
-    HIPCHK(hipFree(c->d_accum));
+    HIPCHK(hipFree(buf));
   }
-  c->d_accum = bigger;
-  c->cap_accum = bytes;
+  buf = bigger;
+  cap = bytes;
   return FR_OK;
+}
+
+// A at `bytes` or more, and Q with it when the context has one or this frame asks for one
+// (with_q): Q is allocated and grown with A, so a live accumulation's Q survives as A does.
+static int grow_accum(fr_ctx* c, size_t bytes, bool with_q) {
+  int rc = grow_kept(c, c->d_accum, c->cap_accum, bytes);
+  if (!rc && (with_q || c->d_sq)) rc = grow_kept(c, c->d_sq, c->cap_sq, c->cap_accum);
+  return rc;
 }
 
 static int grow_events(std::vector<hipEvent_t>& v, size_t n, unsigned flags) {
@@ -476,7 +501,8 @@ void fr_ctx_free(fr_ctx* c) {
     if (s) (void)hipStreamSynchronize(s);
   for (void* d : {static_cast<void*>(c->d_mean), static_cast<void*>(c->d_u8), static_cast<void*>(c->d_cnt),
                   static_cast<void*>(c->d_wcnt), static_cast<void*>(c->d_samples), static_cast<void*>(c->d_running),
-                  static_cast<void*>(c->d_accum)})
+                  static_cast<void*>(c->d_accum), static_cast<void*>(c->d_sq), static_cast<void*>(c->d_err),
+                  static_cast<void*>(c->d_err_part), static_cast<void*>(c->d_err_sum)})
     if (d) (void)hipFree(d);
   for (hipEvent_t e : {c->ev0, c->ev1, c->ev_start, c->ev_copy})
     if (e) (void)hipEventDestroy(e);
@@ -644,9 +670,10 @@ static int render_impl(fr_ctx* c, fr_scene* scene, const fr_camera* cam, const f
   AccumStep step;
   SumAccum acc;
   if (accumulate) {
-    if ((rc = grow_accum(c, fp.running_bytes ? fp.running_bytes : 1u))) return rc;
+    const bool with_q = (p->flags & FR_FLAG_ACCUM_ERROR) != 0;
+    if ((rc = grow_accum(c, fp.running_bytes ? fp.running_bytes : 1u, with_q))) return rc;
     if (!dry && (rc = accum_step(c->accum, accum_key(dc->uid, *cam, *p), p->spp, &step))) return rc;
-    acc = SumAccum{c->d_accum, step.start, static_cast<float>(step.next.samples)};
+    acc = SumAccum{c->d_accum, step.start, static_cast<float>(step.next.samples), with_q ? c->d_sq : nullptr};
   }
   const size_t n_ev = static_cast<size_t>(fp.passes > 0 ? fp.passes : 1);
   if ((rc = grow_events(c->ev_sum, n_ev, hipEventDisableTiming))) return rc;
@@ -661,7 +688,10 @@ static int render_impl(fr_ctx* c, fr_scene* scene, const fr_camera* cam, const f
     if ((rc = enqueue_frame(c, dc, fp, KArgs{kscene(dc, fp), kcam(cam), fp.kp, kw}, sk, fs,
                             accumulate ? &acc : nullptr)))
       return rc;
-    if (accumulate) c->accum = step.next;
+    if (accumulate) {
+      c->accum = step.next;
+      c->accum_kp = fp.kp;
+    }
     c->last = *p;
     c->last_n = dc->ps.facts.n;
     c->pending = true;
@@ -904,6 +934,73 @@ int fr_ctx_accum_info(fr_ctx* c, uint32_t* frames, uint32_t* samples) {
   if (!c) return set_error(FR_EARG, "fr_ctx_accum_info: null ctx");
   if (frames) *frames = c->accum.live ? c->accum.frames : 0u;
   if (samples) *samples = c->accum.live ? c->accum.samples : 0u;
+  return FR_OK;
+}
+
+// The error estimate on demand. Both kernels and the summary's copy go on
+// the sum stream, behind the resolve of every frame enqueued so far (each of them is there),
+// and only that stream is waited for: the pending render's events, counters and stats, A and Q
+// stay as they are.
+int fr_ctx_accum_error(fr_ctx* c, float threshold, fr_accum_error* out) {
+  if (!c || !out) return set_error(FR_EARG, "fr_ctx_accum_error: null argument");
+  if (!(threshold >= 0.0f))
+    return set_error(FR_EARG, "fr_ctx_accum_error: threshold %g must be >= 0 (+infinity counts every pixel)",
+                     static_cast<double>(threshold));
+  const AccumState& a = c->accum;
+  if (!a.live) return set_error(FR_EARG, "fr_ctx_accum_error: no live accumulation (no FR_FLAG_ACCUMULATE frame yet, or reset)");
+  if (!a.has_q || !c->d_sq)
+    return set_error(FR_EARG, "fr_ctx_accum_error: the live accumulation carries no Q: its frames lack FR_FLAG_ACCUM_ERROR");
+  if (a.frames < 2)
+    return set_error(FR_EARG, "fr_ctx_accum_error: %u frame in the accumulation, the estimate needs two", a.frames);
+  SET_DEVICE(c->device);
+  const KParams& kp = c->accum_kp;
+  const uint32_t groups = (kp.P + kSumThreads - 1u) / kSumThreads;
+  int rc;
+  // (a larger map: the sum stream is idle after the last call's wait, nothing reads the old one)
+  if ((rc = grow(c->d_err, c->cap_err, static_cast<size_t>(kp.W) * kp.H * sizeof(float)))) return rc;
+  if ((rc = grow(c->d_err_part, c->cap_err_part, (groups ? groups : 1u) * 2u * sizeof(uint32_t)))) return rc;
+  if (!c->d_err_sum) HIPCHK(hipMalloc(&c->d_err_sum, sizeof(ErrSummary)));
+  c->err_valid = false;
+  HIPCHK(launch_accum_error(c->stream_sum, kp, c->d_accum, c->d_sq, static_cast<float>(a.samples),
+                            static_cast<float>(a.frames - 1u), threshold, c->d_err, c->d_err_part, c->d_err_sum));
+  ErrSummary sum{};
+  HIPCHK(hipMemcpyAsync(&sum, c->d_err_sum, sizeof(sum), hipMemcpyDeviceToHost, c->stream_sum));
+  HIPCHK(hipStreamSynchronize(c->stream_sum));
+  c->err_kp = kp;
+  c->err_valid = true;
+  const ShardStrips ss = shard_strips(kp.H, kp.shard_index, kp.shard_count, false);
+  out->frames = a.frames;
+  out->samples = a.samples;
+  out->pixels = ss.rows * kp.W;
+  out->converged = sum.converged;
+  memcpy(&out->max_rel, &sum.max_bits, sizeof(float));
+  out->threshold = threshold;
+  return FR_OK;
+}
+
+int fr_ctx_download_error(fr_ctx* c, float* rel) {
+  if (!c || !rel) return set_error(FR_EARG, "fr_ctx_download_error: null argument");
+  if (!c->err_valid) return set_error(FR_EARG, "fr_ctx_download_error: no error map (fr_ctx_accum_error first)");
+  SET_DEVICE(c->device);
+  const KParams& kp = c->err_kp;
+  hipStream_t st = c->stream_sum;
+  const size_t row = kp.W;  // elements per row
+  if (kp.shard_count == 1) {
+    HIPCHK(hipMemcpyAsync(rel, c->d_err, row * kp.H * sizeof(float), hipMemcpyDeviceToHost, st));
+  } else {  // this shard's strips, as enqueue_download copies them
+    const ShardStrips ss = shard_strips(kp.H, kp.shard_index, kp.shard_count, false);
+    const size_t first = static_cast<size_t>(kp.shard_index) * kStripRows * row;
+    const size_t pitch = static_cast<size_t>(kp.shard_count) * kStripRows * row;
+    const size_t width = kStripRows * row;
+    if (ss.full)
+      HIPCHK(hipMemcpy2DAsync(rel + first, pitch * 4, c->d_err + first, pitch * 4, width * 4, ss.full,
+                              hipMemcpyDeviceToHost, st));
+    if (ss.has_partial) {
+      const size_t o = static_cast<size_t>(ss.partial) * kStripRows * row;
+      HIPCHK(hipMemcpyAsync(rel + o, c->d_err + o, (kp.H - ss.partial * kStripRows) * row * 4, hipMemcpyDeviceToHost, st));
+    }
+  }
+  HIPCHK(hipStreamSynchronize(st));
   return FR_OK;
 }
 

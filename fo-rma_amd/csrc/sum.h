@@ -17,6 +17,9 @@ struct SumAccum {
   float* accum = nullptr;  // A: 3 f32 per pixel slot of the shard, indexed like `running`
   bool start = false;      // A = S (a new accumulation), else A = A + S
   float divisor = 1.0f;    // (float)n, the samples per pixel A holds after this frame
+  // FR_FLAG_ACCUM_ERROR: Q, indexed like A; the resolve also does Q = S^2 / spp (start) or
+  // Q = Q + S^2 / spp per channel (accum_error.h). Null: the frame carries no Q.
+  float* sq = nullptr;
 };
 
 // wps: words per sample record (2 or 3); the record's form by KParams flags.

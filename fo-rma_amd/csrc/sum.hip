@@ -2,6 +2,7 @@
 // onto its running sum, and at the last pass divides, gamma-corrects and quantises
 // (tracer.rs:170-184). Launched by render.hip through launch_sum (sum.h).
 #include "sum.h"
+#include "accum_error.h"   // accum_sq_term: what a frame adds to Q
 #include "trace_kernel.h"  // slot_xy (with rt_core.h): the trace kernel's pixel-slot order
 
 namespace fr {
@@ -42,8 +43,31 @@ __device__ __forceinline__ V3 accum_resolve(uint32_t q, V3 sum, float* __restric
   return divs(a, divisor);
 }
 
+// The same with the second-moment accumulator (FR_FLAG_ACCUM_ERROR): after A,
+// Q = S^2 / spp (start) or Q = Q + S^2 / spp per channel (accum_error.h), indexed like A. Q's
+// three loads are issued with A's, so both are in flight together; the mean is the one the
+// frame without the flag writes.
+__device__ __forceinline__ V3 accum_resolve_sq(uint32_t q, V3 sum, float fspp, float* __restrict__ accum, int start,
+                                               float divisor, float* __restrict__ sq) {
+  V3 a = sum, s = accum_sq_term(sum, fspp);
+  if (!start) {
+    const V3 a0{accum[3 * q], accum[3 * q + 1], accum[3 * q + 2]};
+    const V3 s0{sq[3 * q], sq[3 * q + 1], sq[3 * q + 2]};
+    a = add(a0, sum);
+    s = add(s0, s);
+  }
+  accum[3 * q] = a.x;
+  accum[3 * q + 1] = a.y;
+  accum[3 * q + 2] = a.z;
+  sq[3 * q] = s.x;
+  sq[3 * q + 1] = s.y;
+  sq[3 * q + 2] = s.z;
+  return divs(a, divisor);
+}
+
 // ACC: empty for the plain kernels, which take the arguments they always took and compile to
-// the same code; {float* accum, int start, float divisor} for the accumulating variant
+// the same code; {float* accum, int start, float divisor} for the accumulating variant, and
+// {float* accum, int start, float divisor, float* sq} for the one that also fills Q
 // (launch_sum). They are arguments of the accumulating kernels alone, not KParams members:
 // KParams is shared with the trace kernel and the scene-kernel cache key.
 template <uint32_t WPS, class... ACC>
@@ -204,7 +228,9 @@ __global__ __launch_bounds__(kSumThreads) FR_SUM_VGPR_CAP void sum_kernel(KParam
     return;
   }
   V3 mean;
-  if constexpr (kAcc)
+  if constexpr (sizeof...(ACC) == 4)
+    mean = accum_resolve_sq(q, sum, static_cast<float>(kp.spp), acc...);
+  else if constexpr (kAcc)
     mean = accum_resolve(q, sum, acc...);
   else
     mean = divs(sum, static_cast<float>(kp.spp));  // tracer.rs:177
@@ -295,7 +321,9 @@ __global__ __launch_bounds__(kSumThreads) FR_SUM_VGPR_CAP void sum_nib_kernel(
   }
   const size_t idx = (static_cast<size_t>(y) * kp.W + x) * 3u;
   V3 mean;
-  if constexpr (kAcc)
+  if constexpr (sizeof...(ACC) == 4)
+    mean = accum_resolve_sq(q, sum, static_cast<float>(kp.spp), acc...);
+  else if constexpr (kAcc)
     mean = accum_resolve(q, sum, acc...);
   else
     mean = divs(sum, static_cast<float>(kp.spp));  // tracer.rs:177
@@ -317,7 +345,17 @@ hipError_t launch_sum(uint32_t wps, uint32_t blocks, hipStream_t stream, const K
   if (acc && last) {  // only a frame's last pass resolves; earlier passes run the plain kernels
     if (!acc->accum || (kp.flags & FR_FLAG_MT_BANDS)) return hipErrorInvalidValue;
     const int start = acc->start ? 1 : 0;
-    if (nib)
+    if (acc->sq) {  // FR_FLAG_ACCUM_ERROR: the instantiations that also fill Q
+      if (nib)
+        hipLaunchKernelGGL((sum_nib_kernel<float*, int, float, float*>), grid, block, 0, stream, kp, samples, running,
+                           out_mean, out_u8, first, last, att, n_prims, acc->accum, start, acc->divisor, acc->sq);
+      else if (wps == 2)
+        hipLaunchKernelGGL((sum_kernel<2, float*, int, float, float*>), grid, block, 0, stream, kp, samples, running,
+                           out_mean, out_u8, first, last, att, n_prims, acc->accum, start, acc->divisor, acc->sq);
+      else
+        hipLaunchKernelGGL((sum_kernel<3, float*, int, float, float*>), grid, block, 0, stream, kp, samples, running,
+                           out_mean, out_u8, first, last, att, n_prims, acc->accum, start, acc->divisor, acc->sq);
+    } else if (nib)
       hipLaunchKernelGGL((sum_nib_kernel<float*, int, float>), grid, block, 0, stream, kp, samples, running, out_mean,
                          out_u8, first, last, att, n_prims, acc->accum, start, acc->divisor);
     else if (wps == 2)

@@ -37,6 +37,9 @@ FR_FLAG_SCENE_JIT = 4  # scene-specialised trace kernel (hiprtc, cached; same im
 FR_FLAG_SCENE_JIT_WAIT = 8  # ... compiled on the render's thread when missing (else in the background)
 FR_FLAG_SCENE_JIT_CACHED = 16  # ... only when already built or on disk; never compiled (one-shot callers)
 FR_FLAG_ACCUMULATE = 32  # the frame's sum joins the context's accumulator; outputs show the running mean
+# with FR_FLAG_ACCUMULATE: the accumulation also carries Q (sum of S^2 / spp), for accum_error()
+FR_FLAG_ACCUM_ERROR = 64
+FR_ERR_FLOOR = 2.0 ** -7  # the relative error's smallest denominator (forma_rt.h)
 FR_JIT_OFF, FR_JIT_USED, FR_JIT_PENDING, FR_JIT_FAILED, FR_JIT_MISS = 0, 1, 2, 3, 4  # fr_ctx_jit_state
 MAX_DEPTH = 50  # tracer.rs:10
 DEFAULT_SEED = 0x5EED
@@ -80,6 +83,14 @@ class FrStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class FrAccumError(C.Structure):
+    _fields_ = [("frames", C.c_uint32), ("samples", C.c_uint32), ("pixels", C.c_uint64), ("converged", C.c_uint64),
+                ("max_rel", C.c_float), ("threshold", C.c_float)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 # Every symbol include/forma_rt.h declares (checked by tests/test_abi.py).
 EXPORTS = (
     "fr_last_error", "fr_abi_version", "fr_device_count",
@@ -95,6 +106,7 @@ EXPORTS = (
     "fr_post_process", "fr_post_process_device", "fr_rgb_to_rgba_device", "fr_ctx_jit_info", "fr_selftest_jit",
     "fr_ctx_prepare", "fr_ctx_jit_state", "fr_jit_wait",
     "fr_ctx_accum_reset", "fr_ctx_accum_info", "fr_mctx_accum_reset", "fr_mctx_accum_info",
+    "fr_ctx_accum_error", "fr_ctx_download_error", "fr_mctx_accum_error",
 )
 
 _lib = None
@@ -192,6 +204,10 @@ def lib():
         L.fr_ctx_accum_info.argtypes = [vp, P(C.c_uint32), P(C.c_uint32)]
         L.fr_mctx_accum_reset.argtypes = [vp]
         L.fr_mctx_accum_info.argtypes = [vp, P(C.c_uint32), P(C.c_uint32)]
+    if hasattr(L, "fr_ctx_accum_error"):  # absent from A/B builds of older sources
+        L.fr_ctx_accum_error.argtypes = [vp, C.c_float, P(FrAccumError)]
+        L.fr_ctx_download_error.argtypes = [vp, f3]
+        L.fr_mctx_accum_error.argtypes = [vp, C.c_float, P(FrAccumError), f3]
     _lib = L
     return L
 
@@ -418,13 +434,15 @@ def make_params(width, height, spp, max_depth=MAX_DEPTH, seed=DEFAULT_SEED, shar
     the compiled-in kernel, same bits), "wait" (compile on the render's thread if needed) or
     "cached" (the scene kernel only if already built or on disk; never a compile).
     accumulate: FR_FLAG_ACCUMULATE, the frame refines the context's accumulation of this view
-    (forma_rt.h); give every frame its own seed."""
+    (forma_rt.h); give every frame its own seed. accumulate="error": FR_FLAG_ACCUM_ERROR as
+    well, the accumulation carries what accum_error() needs (same picture)."""
     p = FrParams()
     p.width, p.height, p.spp, p.max_depth, p.seed = width, height, spp, max_depth, seed
     p.strip_rows, p.shard_index, p.shard_count = 8, shard_index, shard_count
     p.flags = ((FR_FLAG_WRITE_U8 if write_u8 else 0) | (FR_FLAG_MT_BANDS if mt_bands else 0) |
                (FR_FLAG_SCENE_JIT if scene_jit else 0) | (FR_FLAG_SCENE_JIT_WAIT if scene_jit == "wait" else 0) |
-               (FR_FLAG_SCENE_JIT_CACHED if scene_jit == "cached" else 0) | (FR_FLAG_ACCUMULATE if accumulate else 0))
+               (FR_FLAG_SCENE_JIT_CACHED if scene_jit == "cached" else 0) | (FR_FLAG_ACCUMULATE if accumulate else 0) |
+               (FR_FLAG_ACCUM_ERROR if isinstance(accumulate, str) and accumulate == "error" else 0))
     return p
 
 
@@ -492,6 +510,8 @@ class RenderContext:
 
     def render(self, scene, cam, params):
         check(lib().fr_ctx_render(self._h, scene._h, C.byref(cam), C.byref(params)))
+        if params.flags & FR_FLAG_ACCUMULATE:
+            self._accum_shape = (params.height, params.width)
 
     def sync(self):
         st = FrStats()
@@ -546,6 +566,32 @@ class RenderContext:
         frames, samples = C.c_uint32(0), C.c_uint32(0)
         check(lib().fr_ctx_accum_info(self._h, C.byref(frames), C.byref(samples)))
         return frames.value, samples.value
+
+    def accum_error(self, threshold, want_map=False):
+        """The error estimate of the live accumulation (frames rendered with
+        make_params(accumulate="error"), two or more): a dict of frames, samples, pixels,
+        converged (pixels whose relative standard error is <= threshold), max_rel and
+        threshold. Waits for the frames enqueued so far. want_map: (summary, rel) with rel the
+        [H, W] f32 map, rows of other shards NaN."""
+        e = FrAccumError()
+        check(lib().fr_ctx_accum_error(self._h, float(threshold), C.byref(e)))
+        if not want_map:
+            return e.as_dict()
+        return e.as_dict(), self.download_error()
+
+    def download_error(self, rel=None):
+        """The map of the last accum_error() as [H, W] f32: this shard's rows are written into
+        `rel` (a new NaN-filled array when None; the shape is the last accumulating frame's)."""
+        if rel is None:
+            rel = np.full(self._err_shape(), np.nan, dtype=np.float32)
+        check(lib().fr_ctx_download_error(self._h, rel.ctypes.data_as(C.POINTER(C.c_float))))
+        return rel
+
+    def _err_shape(self):
+        shape = getattr(self, "_accum_shape", None)
+        if shape is None:
+            raise ForMaError(FR_EARG, "download_error: pass `rel` ([H, W] f32) on a context that rendered elsewhere")
+        return shape
 
     def jit_state(self):
         """FR_JIT_OFF / USED / PENDING / FAILED for the last render (fr_ctx_jit_state)."""
@@ -639,6 +685,15 @@ class MultiContext:
         check(lib().fr_mctx_accum_info(self._h, C.byref(frames), C.byref(samples)))
         return frames.value, samples.value
 
+    def accum_error(self, threshold, want_map=False):
+        """RenderContext.accum_error over every shard: pixels and converged are the shards'
+        sums, max_rel their maximum; want_map: (summary, the whole [H, W] f32 map)."""
+        e = FrAccumError()
+        rel = np.full(self._shape[:2], np.nan, dtype=np.float32) if want_map else None
+        check(lib().fr_mctx_accum_error(self._h, float(threshold), C.byref(e),
+                                        rel.ctypes.data_as(C.POINTER(C.c_float)) if want_map else None))
+        return (e.as_dict(), rel) if want_map else e.as_dict()
+
     def context(self, i):
         """The i-th shard's RenderContext view (not owned: do not close it)."""
         h = C.c_void_p()
@@ -657,6 +712,26 @@ class MultiContext:
             self.close()
         except Exception:
             pass
+
+
+def render_converged(ctx, scene, cam, w, h, spp, max_depth, seed, target, fraction=1.0, max_frames=64, check_every=1,
+                     scene_jit=False):
+    """Accumulating frames of `spp` samples on `ctx` (frame k = 1, 2, ... has seed `seed + k`)
+    until, at a checked frame k >= 2 (every check_every-th), converged >= fraction * pixels for
+    the relative standard error `target` (accum_error), or max_frames are done. Starts a new
+    accumulation. Returns (mean[H,W,3] f32, u8[H,W,3], the last summary, or None if none was
+    taken)."""
+    ctx.accum_reset()
+    summary = None
+    for k in range(1, max_frames + 1):
+        ctx.render(scene, cam, make_params(w, h, spp, max_depth, seed + k, accumulate="error", scene_jit=scene_jit))
+        if k >= 2 and k % check_every == 0:
+            summary = ctx.accum_error(target)
+            if summary["converged"] >= fraction * summary["pixels"]:
+                break
+    ctx.sync()
+    mean, u8 = ctx.download(w, h)
+    return mean, u8, summary
 
 
 def render(scene, cam, width, height, spp, max_depth=MAX_DEPTH, seed=DEFAULT_SEED, device=0, shard_index=0,
@@ -738,7 +813,8 @@ class TraceModel:
         model.pixels is). The view keeps the page-locked block alive, so an array returned
         here stays valid memory after the model is closed or collected; copy it to keep a
         frame past the next update(). accumulate: the frame joins the context's accumulation
-        (FR_FLAG_ACCUMULATE) and the image is the mean of every frame in it."""
+        (FR_FLAG_ACCUMULATE) and the image is the mean of every frame in it; "error": the
+        accumulation also carries the error estimate (model.ctx.accum_error)."""
         ctx = self.context()
         ctx.render(scene, self.scene.camera, make_params(self.width, self.height, 1, max_depth, seed,
                                                          accumulate=accumulate))
@@ -773,7 +849,9 @@ def update(model, keys, delta_time, max_depth=MAX_DEPTH, accumulate=False):
     """tracer.rs:30-55: key bitmask 00EQADWS -> camera.orbit(delta), then one 1-spp frame
     into model.pixels. Each frame draws from its own RNG key. accumulate: while no key is
     pressed the frames add up on the model's context and model.pixels converges (the mean of
-    every frame since the camera last moved); a key press moves the camera, which starts anew."""
+    every frame since the camera last moved); a key press moves the camera, which starts anew.
+    accumulate="error": the same picture, and model.ctx.accum_error(threshold) tells how far the
+    accumulation has converged (FR_FLAG_ACCUM_ERROR)."""
     d = (C.c_float * 3)()
     check(lib().fr_update_delta(int(keys) & 0xFF, float(delta_time), d))
     camera_orbit(model.scene.camera, list(d))

@@ -58,7 +58,8 @@ extern "C" {
                             6: FR_FLAG_SCENE_JIT compiles in the background (renders never wait),
                                FR_FLAG_SCENE_JIT_WAIT, fr_ctx_jit_state, fr_jit_wait
                                (still 6, additive: FR_FLAG_ACCUMULATE, fr_ctx_accum_reset / _info,
-                               fr_mctx_accum_reset / _info) */
+                               fr_mctx_accum_reset / _info; FR_FLAG_ACCUM_ERROR,
+                               fr_ctx_accum_error, fr_ctx_download_error, fr_mctx_accum_error) */
 
 /* error codes */
 #define FR_OK 0
@@ -117,10 +118,36 @@ extern "C" {
    frame's; otherwise, and after fr_ctx_accum_reset, it starts a new one. seed and spp may
    differ from frame to frame (give every frame its own seed). Plain renders on the same
    context in between neither read nor disturb A and n. A is plain f32 without compensation:
-   it stops improving in the region of 2^24 samples per pixel; a frame that would take n past
-   2^32 - 1 is FR_EARG. FR_EARG with FR_FLAG_MT_BANDS (save_image_mt has its own averaging)
+   it stops improving in the region of 2^24 samples per pixel (so does Q of
+   FR_FLAG_ACCUM_ERROR, whose estimate moreover cannot resolve a relative error under about
+   2^-12 sqrt(K) after K frames: see there); a frame that would take n past 2^32 - 1 is FR_EARG. FR_EARG with FR_FLAG_MT_BANDS (save_image_mt has its own averaging)
    and through fr_render_hip / fr_render_hip_multi (their context dies with the call). */
 #define FR_FLAG_ACCUMULATE 32u
+/* With FR_FLAG_ACCUMULATE only: the accumulation also carries a second-moment accumulator Q
+   (3 f32 per pixel of the shard, indexed, kept and grown like A), from which
+   fr_ctx_accum_error estimates each pixel's remaining noise. After A is updated the frame does,
+   per channel and in f32 with every operation rounded once and nothing fused,
+   q = (S * S) / (float)spp, then Q = q when the frame starts an accumulation, else Q = Q + q.
+   The mean and the u8 image are exactly those of the frame without this flag. The bit is part
+   of what a frame must share with the previous accumulating frame to continue its accumulation
+   (see FR_FLAG_ACCUMULATE): a frame whose bit differs starts a new one, so Q never misses a
+   frame of the accumulation it describes. FR_EARG without FR_FLAG_ACCUMULATE and with spp 0.
+
+   The estimate, for a pixel with n samples in K >= 2 frames, fn = (float)n, fk = (float)(K - 1),
+   per channel c, every operation rounded once in f32:
+     m_c = A_c / fn
+     v_c = max((Q_c - A_c * m_c) / fk, 0)          a NaN reads 0
+     err = sqrt(((v_r + v_g) + v_b) / fn)          standard error of the summed channels' mean
+     den = max((m_r + m_g) + m_b, FR_ERR_FLOOR)    a NaN reads FR_ERR_FLOOR
+     rel = err / den, or 0 where (m_r + m_g) + m_b is NaN or infinite: such a pixel does not
+           change with more frames, so there is nothing to wait for
+   S_k has mean spp_k mu and variance spp_k sigma^2, so (sum_k S_k^2 / spp_k - A^2 / n) / (K - 1)
+   is an unbiased estimate of the per-sample variance sigma^2 for frames of any spp, and v_c / n
+   is the variance of the mean. rel is never NaN and never negative. Q - A^2 / n in f32 loses
+   everything below about K 2^-24 of m^2: a pixel whose true relative error is under about
+   2^-12 sqrt(K) reads as 0 or as noise of that size, far under one u8 step. */
+#define FR_FLAG_ACCUM_ERROR 64u
+#define FR_ERR_FLOOR 0.0078125f /* 2^-7 */
 /* fr_ctx_jit_state: which trace kernel the last render (or fr_ctx_prepare) ran */
 #define FR_JIT_OFF 0     /* compiled-in kernel: not asked for, a BVH scene, or > 64 primitives */
 #define FR_JIT_USED 1    /* the scene-specialised kernel */
@@ -273,6 +300,25 @@ int fr_ctx_accum_reset(fr_ctx* ctx);
 /* Frames and samples per pixel in the accumulator (0, 0 when there is none). Host-side, as of
    the last enqueued frame; no sync. Either may be NULL. */
 int fr_ctx_accum_info(fr_ctx* ctx, uint32_t* frames, uint32_t* samples);
+/* The error estimate of the live accumulation (FR_FLAG_ACCUM_ERROR) and its summary. */
+typedef struct fr_accum_error { /* 32 bytes */
+  uint32_t frames, samples;     /* K and n the estimate was taken at */
+  uint64_t pixels;              /* pixels of the shard(s) */
+  uint64_t converged;           /* of them, rel <= threshold */
+  float max_rel, threshold;     /* the largest rel of those pixels; the threshold asked for */
+} fr_accum_error;
+/* Computes rel (FR_FLAG_ACCUM_ERROR) for every pixel of this context's shard as of the last
+   enqueued accumulating frame, into a W x H f32 map on the device, and its summary: two small
+   kernels behind every enqueued frame's resolve, then a wait for them alone. The pending
+   render, its stats, A and Q are left as they are, so it may be called between streamed
+   frames. Integer counts and a maximum over bit patterns: the same accumulation gives the
+   same summary bit for bit. FR_EARG when the context has no live accumulation, when the live
+   one carries no Q, when it has fewer than two frames, and for a NaN or negative threshold
+   (+infinity is allowed and counts every pixel). */
+int fr_ctx_accum_error(fr_ctx* ctx, float threshold, fr_accum_error* out);
+/* Copies the map of the last fr_ctx_accum_error into rel (W x H f32, row-major): this shard's
+   rows only, the others are left untouched. */
+int fr_ctx_download_error(fr_ctx* ctx, float* rel);
 
 /* ---- persistent multi-device context (tracer.rs:83-134 render_mt, one device per shard) ----
    Entry i of `devices` renders row shard i of n of every frame on its own fr_ctx (device
@@ -297,6 +343,9 @@ int fr_mctx_download(fr_mctx* mctx, float* mean_rgb, uint8_t* rgb8);
    shard's accumulation and report shard 0's figures (all shards agree by construction). */
 int fr_mctx_accum_reset(fr_mctx* mctx);
 int fr_mctx_accum_info(fr_mctx* mctx, uint32_t* frames, uint32_t* samples);
+/* fr_ctx_accum_error on every shard: pixels and converged are the shards' sums, max_rel their
+   maximum, frames and samples shard 0's. rel, when not NULL, receives the whole W x H map. */
+int fr_mctx_accum_error(fr_mctx* mctx, float threshold, fr_accum_error* out, float* rel /* or NULL */);
 
 /* Page-locked host memory (hipHostMalloc) for fr_ctx_download_async targets. */
 int fr_host_alloc(size_t bytes, void** out);

@@ -2,13 +2,16 @@
 simple scene (get_simple_scene, max_depth 50) with an orbiting camera, on the model's
 persistent render context, including the u8 download into model.pixels.
 
-    python tools/time_update.py [W H] [frames] [--accumulate]
+    python tools/time_update.py [W H] [frames] [--accumulate | --error[=N]]
 
 Prints one JSON line: median / p90 host wall time per update() call, and the same frame
 through the one-shot fr_render_hip (a context made and freed per call) for comparison.
 --accumulate: the timed calls are update(..., accumulate=True) with no key pressed, so the
 camera stands still and every frame continues the accumulation (the resolve's read and write
-of the accumulator); "accum_frames" then says how many frames the last picture holds."""
+of the accumulator); "accum_frames" then says how many frames the last picture holds.
+--error[=N]: the same frames with accumulate="error" (the resolve also reads and writes Q), and
+an accum_error(2^-4) after every N-th frame (default 10) inside the timed call; "error_ms_median"
+is the host time of those calls alone and "error" the last summary."""
 import json
 import os
 import sys
@@ -20,19 +23,26 @@ import forma_rt as fr  # noqa: E402
 
 
 def main():
-    argv = [a for a in sys.argv[1:] if a != "--accumulate"]
-    accumulate = len(argv) != len(sys.argv) - 1
+    argv = [a for a in sys.argv[1:] if not a.startswith("--")]
+    opts = [a for a in sys.argv[1:] if a.startswith("--")]
+    err = [a for a in opts if a.split("=")[0] == "--error"]
+    every = int(err[0].split("=")[1]) if err and "=" in err[0] else 10
+    accumulate = "error" if err else "--accumulate" in opts
     w, h = (int(argv[0]), int(argv[1])) if len(argv) > 1 else (1920, 1080)
     frames = int(argv[2]) if len(argv) > 2 else 30
     m = fr.create_model(w, h)
     fr.update(m, 0b001000, 1.0 / 60)  # first frame: context, scene upload, buffers
     if accumulate:
-        fr.update(m, 0, 1.0 / 60, accumulate=True)  # the accumulator's allocation
-    ts = []
+        fr.update(m, 0, 1.0 / 60, accumulate=accumulate)  # the accumulator's allocation
+    ts, es, summary = [], [], None
     for k in range(frames):
         t = time.perf_counter()
         if accumulate:
-            fr.update(m, 0, 1.0 / 60, accumulate=True)
+            fr.update(m, 0, 1.0 / 60, accumulate=accumulate)
+            if err and (k + 1) % every == 0:
+                te = time.perf_counter()
+                summary = m.ctx.accum_error(2.0 ** -4)
+                es.append((time.perf_counter() - te) * 1e3)
         else:
             fr.update(m, 0b001000 if k % 2 else 0b000100, 1.0 / 60)
         ts.append((time.perf_counter() - t) * 1e3)
@@ -45,8 +55,13 @@ def main():
         one.append((time.perf_counter() - t) * 1e3)
     ts.sort()
     one.sort()
+    es.sort()
+    extra = {}
+    if err:
+        extra = {"error_every": every, "error_calls": len(es),
+                 "error_ms_median": round(es[len(es) // 2], 3) if es else None, "error": summary}
     print(json.dumps({"workload": f"update() simple scene {w}x{h} 1spp depth 50", "frames": frames,
-                      "accumulate": accumulate, "accum_frames": accum_frames,
+                      "accumulate": bool(accumulate), "accum_frames": accum_frames, **extra,
                       "ms_median": round(ts[len(ts) // 2], 3), "ms_p90": round(ts[int(0.9 * len(ts))], 3),
                       "kernel_ms": round(st["kernel_ms"], 3), "fps_median": round(1e3 / ts[len(ts) // 2], 1),
                       "one_shot_render_ms_median": round(one[len(one) // 2], 3),
