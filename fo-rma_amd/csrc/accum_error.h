@@ -66,5 +66,23 @@ struct ErrSummary {
 hipError_t launch_accum_error(hipStream_t stream, const KParams& kp, const float* accum, const float* sq, float fn,
                               float fk, float threshold, float* err_map, uint32_t* partials, ErrSummary* summary);
 
+// fr_ctx_adapt's summary on the device: 32 bytes.
+struct AdaptSummary {
+  unsigned long long converged;      // pixels with rel <= threshold
+  unsigned long long active_pixels;  // image pixels in the list's tiles
+  uint32_t max_bits;                 // the largest rel, as its bits
+  uint32_t active_tiles;             // the list's length
+  uint32_t pad[2];
+};
+
+// The estimate of a tiled accumulation: rel from each tile's own n_t and K_t
+// into err_map, then either (adapt) the selection, the ordered active tile list and *adapt,
+// or (summary) accum_error_reduce's *summary. kp: the whole shard's constants.
+// tile_pixels, list: one uint32 per tile of the shard.
+hipError_t launch_adapt(hipStream_t stream, const KParams& kp, const float* accum, const float* sq,
+                        const uint32_t* n_t, const uint32_t* k_t, float threshold, uint32_t min_samples,
+                        float* err_map, uint32_t* partials, uint32_t* tile_pixels, uint32_t* list,
+                        AdaptSummary* adapt, ErrSummary* summary);
+
 }  // namespace fr
 #endif

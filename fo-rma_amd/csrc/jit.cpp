@@ -398,6 +398,7 @@ void unload_evicted(const Module& m) {
   }
   (void)hipModuleUnload(m.mod);
   if (cur >= 0) (void)hipSetDevice(cur);
+  (void)hipGetLastError();  // results ignored on purpose: not left for a render's check to find
 }
 
 }  // namespace
@@ -445,6 +446,26 @@ void jit_note_launch(const std::shared_ptr<void>& pin, hipStream_t stream) {
   if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) return;
   (void)hipEventRecord(ev, stream);
   u->last.emplace_back(stream, ev);
+}
+
+void jit_forget_streams(const hipStream_t* streams, int n) {
+  Registry& R = reg();
+  std::lock_guard<std::mutex> lk(R.mu);
+  for (auto& km : R.modules) {
+    ModuleUse* u = km.second.pin.get();
+    std::lock_guard<std::mutex> g(u->mu);
+    auto keep = u->last.begin();
+    for (auto& se : u->last) {
+      bool gone = false;
+      for (int i = 0; i < n; ++i) gone = gone || se.first == streams[i];
+      if (gone)
+        (void)hipEventDestroy(se.second);  // (its launch has finished: the stream was drained)
+      else
+        *keep++ = se;
+    }
+    u->last.erase(keep, u->last.end());
+  }
+  (void)hipGetLastError();  // results ignored on purpose: not left for a later check to find
 }
 
 int jit_trace_kernel(int device, const JitSpec& spec, bool wait, hipFunction_t* out, JitStats* stats,

@@ -49,6 +49,11 @@ int jit_trace_kernel(int device, const JitSpec& spec, bool wait, hipFunction_t* 
 // After a launch of a module's kernel on `stream`: the module is unloaded (LRU eviction)
 // only after this launch has finished (an event on the stream, not a device drain).
 void jit_note_launch(const std::shared_ptr<void>& pin, hipStream_t stream);
+// A context is about to destroy `streams` (already drained): every loaded module drops the
+// events it recorded on them. An event must not outlive the stream it was last recorded on:
+// a later query or wait of it (a module's unload, the pruning in jit_note_launch) was seen to
+// fail with hipErrorCapturedEvent once the stream was gone, and a new stream may reuse the handle.
+void jit_forget_streams(const hipStream_t* streams, int n);
 
 // Block until the background worker has no compile queued or running.
 int jit_wait_all();

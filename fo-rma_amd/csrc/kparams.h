@@ -42,6 +42,10 @@ constexpr uint32_t kNibbleMaxPrims = 15;
 constexpr uint32_t kNibbleUnit = 15;
 constexpr uint32_t KF_NIBBLE = 1u << 29;           // internal: 8-B deferred records
 constexpr uint32_t KF_DIFFUSE = 1u << 28;          // internal: no metal/dielectric (trace_kernel MAT = 1)
+// internal: an adaptive frame, KParams::tile_list maps its compact tiles (set by the driver with
+// the pointer, after the plan: it is no part of the kernel choice). The seeding tests this bit
+// of a word it already holds instead of the pointer.
+constexpr uint32_t KF_LIST = 1u << 27;
 // RNG contract, not tuning: one stream per 16-sample block (oracle.cpp agrees; the goldens pin it)
 constexpr uint32_t kBlockSamples = 16;  // samples per RNG stream (numerics contract)
 // The last block of a pixel with more than one block is split into sub-blocks of
@@ -81,6 +85,11 @@ struct KParams {
   // when spp > kBlockSamples and this pass holds it): item = n_coarse + k * P + q for
   // sub-block k; n_coarse = n_items when the pass has none
   uint32_t n_coarse, b_fine;
+  // FR_FLAG_ADAPTIVE: the context's active tile list, ascending real tiles
+  // of the shard. Non-null only for an adaptive frame, whose n_tiles, P, items and magics are
+  // then the list's: a compact slot q stands for real slot (tile_list[q >> 6] << 6) | (q & 63)
+  // (slot_xy). Null, and KF_LIST clear, for every other frame.
+  const uint32_t* tile_list;
 };
 
 // Unsigned 32-bit division by the invariant n_tiles: q = (t + ((x - t) >> s1)) >> s2 with

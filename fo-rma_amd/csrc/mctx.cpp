@@ -92,7 +92,7 @@ int fr_mctx_render(fr_mctx* m, fr_scene* scene, const fr_camera* cam, const fr_p
   m->t0 = std::chrono::steady_clock::now();
   // enqueue every shard and its gather, then return: the devices run concurrently
   // (params' flags go to every shard as they are: with FR_FLAG_ACCUMULATE each shard's context
-  // accumulates its own strips)
+  // accumulates its own strips, with FR_FLAG_ADAPTIVE it traces its own tile list)
   for (int i = 0; i < n; ++i) {
     p.shard_index = static_cast<uint32_t>(i);
     if ((rc = fr_ctx_render(m->ctx[i], scene, cam, &p))) return set_error(rc, "shard %d: %s", i, fr_last_error());
@@ -180,6 +180,30 @@ int fr_mctx_accum_error(fr_mctx* m, float threshold, fr_accum_error* out, float*
     agg.max_rel = std::max(agg.max_rel, e.max_rel);  // (rel is never NaN)
   }
   agg.threshold = threshold;
+  *out = agg;
+  return FR_OK;
+}
+
+// Every shard's selection (fr_ctx_adapt): counts add, the maximum is the shards' maximum.
+int fr_mctx_adapt(fr_mctx* m, float threshold, uint32_t min_samples, fr_adapt_info* out) {
+  if (!m || m->ctx.empty() || !out) return set_error(FR_EARG, "fr_mctx_adapt: null argument");
+  fr_adapt_info agg;
+  memset(&agg, 0, sizeof(agg));
+  for (size_t i = 0; i < m->ctx.size(); ++i) {
+    fr_adapt_info e;
+    const int rc = fr_ctx_adapt(m->ctx[i], threshold, min_samples, &e);
+    if (rc) return set_error(rc, "shard %zu: %s", i, std::string(fr_last_error()).c_str());
+    agg.frames = std::max(agg.frames, e.frames);
+    agg.samples = std::max(agg.samples, e.samples);
+    agg.tiles += e.tiles;
+    agg.active_tiles += e.active_tiles;
+    agg.pixels += e.pixels;
+    agg.active_pixels += e.active_pixels;
+    agg.converged += e.converged;
+    agg.max_rel = std::max(agg.max_rel, e.max_rel);  // (rel is never NaN)
+  }
+  agg.threshold = threshold;
+  agg.min_samples = min_samples;
   *out = agg;
   return FR_OK;
 }

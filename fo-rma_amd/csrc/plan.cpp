@@ -53,6 +53,9 @@ int check_params(const fr_params* p) {
     return set_error(FR_EARG, "FR_FLAG_ACCUMULATE with FR_FLAG_MT_BANDS: save_image_mt has its own averaging");
   if ((p->flags & FR_FLAG_ACCUM_ERROR) && !(p->flags & FR_FLAG_ACCUMULATE))
     return set_error(FR_EARG, "FR_FLAG_ACCUM_ERROR without FR_FLAG_ACCUMULATE: the error estimate is an accumulation's");
+  if ((p->flags & FR_FLAG_ADAPTIVE) && (~p->flags & (FR_FLAG_ACCUMULATE | FR_FLAG_ACCUM_ERROR)))
+    return set_error(FR_EARG, "FR_FLAG_ADAPTIVE needs FR_FLAG_ACCUMULATE | FR_FLAG_ACCUM_ERROR: its tile list comes "
+                     "from an accumulation's error estimate");
   if ((p->flags & FR_FLAG_ACCUM_ERROR) && p->spp == 0)
     return set_error(FR_EARG, "FR_FLAG_ACCUM_ERROR with spp 0: a frame without samples has no S^2 / spp");
   return FR_OK;
@@ -89,7 +92,7 @@ static size_t sample_buffer_cap(size_t device_bytes, const PlanEnv& env) {
 }
 
 int make_plan(const fr_params& p, float cam_reach, const SceneFacts& sf, int num_cus, size_t device_bytes,
-              const PlanEnv& env, bool dry, const PlanHistory& hist, FramePlan* out) {
+              const PlanEnv& env, bool dry, const PlanHistory& hist, FramePlan* out, const uint32_t* active_tiles) {
   FramePlan fp;
   const bool mt = (p.flags & FR_FLAG_MT_BANDS) != 0;
   // the node cull holds for origins within the scene's reach (bvh.h bvh_origin_reach)
@@ -110,14 +113,17 @@ int make_plan(const fr_params& p, float cam_reach, const SceneFacts& sf, int num
   kp.shard_index = p.shard_index;
   kp.shard_count = p.shard_count;
   // (an accumulating frame is planned, traced and cached as the plain frame: the flag stops here)
-  kp.flags = p.flags & ~(FR_FLAG_ACCUMULATE | FR_FLAG_ACCUM_ERROR);
+  kp.flags = p.flags & ~(FR_FLAG_ACCUMULATE | FR_FLAG_ACCUM_ERROR | FR_FLAG_ADAPTIVE);
   kp.tiles_per_row = (p.width + 7u) / 8u;
   kp.band_h = p.height / 4u;
   kp.n_tiles = shard_strips(p.height, p.shard_index, p.shard_count, mt).count * kp.tiles_per_row;
+  // an adaptive frame: the compact tiles of the active list (at most the shard's)
+  if (active_tiles) kp.n_tiles = std::min(*active_tiles, kp.n_tiles);
   kp.P = kp.n_tiles * 64u;
   fastdiv_magic(kp.n_tiles, kp.tiles_magic, kp.tiles_shift);
   fastdiv_magic(kp.tiles_per_row, kp.row_magic, kp.row_shift);
-  fp.nblocks = (p.spp + kBlockSamples - 1) / kBlockSamples;
+  // (an empty list: no blocks, so no passes, no items and no buffers)
+  fp.nblocks = active_tiles && !kp.P ? 0u : (p.spp + kBlockSamples - 1) / kBlockSamples;
   // sample slots per item: a frame of spp < 16 (update()'s 1-spp frames) needs only spp
   kp.ks = p.spp < kBlockSamples ? (p.spp ? p.spp : 1u) : kBlockSamples;
   fp.small_depth = p.max_depth <= kSmallDepth && sf.n < 65536u;
@@ -266,6 +272,16 @@ int accum_step(const AccumState& prev, const AccumKey& key, uint32_t spp, AccumS
   s.next.samples = s.start ? spp : prev.samples + spp;
   s.next.has_q = key.error != 0;
   *out = s;
+  return FR_OK;
+}
+
+int adaptive_step(const AccumState& prev, const TiledState& tiled, const AccumKey& key, AdaptiveFrame* out) {
+  if (!(prev.live && same_view(prev.key, key)))
+    return set_error(FR_EARG, "FR_FLAG_ADAPTIVE: the frame would start a new accumulation, which has no tile list "
+                     "(render plain accumulating frames, then fr_ctx_adapt)");
+  if (!tiled.tiled)
+    return set_error(FR_EARG, "FR_FLAG_ADAPTIVE: the live accumulation has no tile list (fr_ctx_adapt first)");
+  *out = tiled.active_tiles ? AdaptiveFrame::kTrace : AdaptiveFrame::kEmpty;
   return FR_OK;
 }
 

@@ -159,8 +159,13 @@ struct FramePlan {
 };
 
 // FR_OK, or FR_EARG (fr_last_error) when the shard exceeds the 32-bit work-item range.
+// active_tiles: null for every frame but an adaptive one (FR_FLAG_ADAPTIVE), whose n_tiles, P,
+// magics, sample buffer and passes then follow from the length of the context's active tile
+// list instead of the shard's tile count; 0 gives a plan without passes. The plan stays a pure
+// function of its arguments (KParams::tile_list is the driver's to set).
 int make_plan(const fr_params& p, float cam_reach, const SceneFacts& sf, int num_cus, size_t device_bytes,
-              const PlanEnv& env, bool dry, const PlanHistory& hist, FramePlan* out);
+              const PlanEnv& env, bool dry, const PlanHistory& hist, FramePlan* out,
+              const uint32_t* active_tiles = nullptr);
 
 struct PassPlan {
   uint32_t b0 = 0, nb = 0, n_items = 0, n_coarse = 0, b_fine = 0;
@@ -206,6 +211,27 @@ struct AccumStep {
 // is live and of the same view, else starts anew. FR_EARG (fr_last_error) when continuing
 // would take n past 2^32 - 1; *out is then untouched.
 int accum_step(const AccumState& prev, const AccumKey& key, uint32_t spp, AccumStep* out);
+
+// ---- adaptive sampling (FR_FLAG_ADAPTIVE) ----------------------------
+// fr_ctx_adapt makes the live accumulation tiled: from then on every 8x8 tile of the shard has
+// its own sample and frame counts on the device, and the context holds a list of the tiles an
+// adaptive frame traces. AccumState's frames and samples stay the host's totals: the frames
+// enqueued and the sum of their spp, the largest count a tile can have. The tiled state dies
+// with the accumulation (a frame that starts a new one, fr_ctx_accum_reset).
+struct TiledState {
+  bool tiled = false;
+  uint32_t tiles = 0;          // tiles of the shard (each holds at least one image pixel)
+  uint32_t active_tiles = 0;   // length of the list as of the last fr_ctx_adapt
+  uint64_t active_pixels = 0;  // image pixels in the list's tiles
+};
+
+enum class AdaptiveFrame { kTrace, kEmpty };
+
+// An adaptive frame seen through `key` on accumulation `prev`: FR_EARG (fr_last_error) when it
+// would start a new accumulation or the live one is not tiled, before anything is enqueued;
+// kEmpty when the list is empty (nothing is traced and no state moves); else kTrace, and the
+// frame then goes through accum_step like any accumulating frame.
+int adaptive_step(const AccumState& prev, const TiledState& tiled, const AccumKey& key, AdaptiveFrame* out);
 
 // ---- kernel choice ----------------------------------------------------------------
 

@@ -25,6 +25,7 @@
 #include <chrono>
 #include <cmath>
 #include <string>
+#include <vector>
 
 #include "accum_error.h"
 #include "hipchk.h"
@@ -42,6 +43,7 @@ static_assert(sizeof(fr_camera) == 104, "fr_camera layout");
 static_assert(sizeof(fr_params) == 40, "fr_params layout");
 static_assert(sizeof(fr_stats) == 72, "fr_stats layout");
 static_assert(sizeof(fr_accum_error) == 32, "fr_accum_error layout");
+static_assert(sizeof(fr_adapt_info) == 56, "fr_adapt_info layout");
 
 struct DeviceCopy {
   int device = -1;
@@ -181,6 +183,20 @@ struct fr_ctx {
   size_t cap_err = 0, cap_err_part = 0;
   KParams err_kp{};
   bool err_valid = false;
+  // Adaptive sampling (FR_FLAG_ADAPTIVE), one uint32 per tile of the shard
+  // each: the tiled accumulation's counts n_t and K_t, which the resolves maintain on the sum
+  // stream; the active tile list an adaptive frame's trace and sums read; the selection's
+  // per-tile scratch. `tiled`: the host's record (plan.h), dead with the accumulation.
+  uint32_t* d_nt = nullptr;
+  uint32_t* d_kt = nullptr;
+  uint32_t* d_list = nullptr;
+  uint32_t* d_tile_px = nullptr;
+  AdaptSummary* d_adapt_sum = nullptr;
+  size_t cap_nt = 0, cap_kt = 0, cap_list = 0, cap_tile_px = 0;
+  TiledState tiled;
+  // the last render was adaptive: the image pixels it traced (fr_stats), or none (empty list)
+  bool last_adaptive = false, last_empty = false;
+  uint64_t last_active_pixels = 0;
   int num_cus = 0;
   size_t device_bytes = 0;  // HBM size (the sample buffer budget's default)
   fr_params last{};
@@ -499,10 +515,17 @@ void fr_ctx_free(fr_ctx* c) {
   // every stream drained before any buffer or event it may still use goes
   for (hipStream_t s : {c->stream, c->stream2, c->stream_sum, c->stream_copy})
     if (s) (void)hipStreamSynchronize(s);
+  // the scene kernels' launch events on this context's trace streams go before the streams do
+  {
+    const hipStream_t ts[2] = {c->stream, c->stream2};
+    jit_forget_streams(ts, 2);
+  }
   for (void* d : {static_cast<void*>(c->d_mean), static_cast<void*>(c->d_u8), static_cast<void*>(c->d_cnt),
                   static_cast<void*>(c->d_wcnt), static_cast<void*>(c->d_samples), static_cast<void*>(c->d_running),
                   static_cast<void*>(c->d_accum), static_cast<void*>(c->d_sq), static_cast<void*>(c->d_err),
-                  static_cast<void*>(c->d_err_part), static_cast<void*>(c->d_err_sum)})
+                  static_cast<void*>(c->d_err_part), static_cast<void*>(c->d_err_sum), static_cast<void*>(c->d_nt),
+                  static_cast<void*>(c->d_kt), static_cast<void*>(c->d_list), static_cast<void*>(c->d_tile_px),
+                  static_cast<void*>(c->d_adapt_sum)})
     if (d) (void)hipFree(d);
   for (hipEvent_t e : {c->ev0, c->ev1, c->ev_start, c->ev_copy})
     if (e) (void)hipEventDestroy(e);
@@ -655,10 +678,26 @@ static int render_impl(fr_ctx* c, fr_scene* scene, const fr_camera* cam, const f
   // The previous frame of this context still running (its end event pending): frames are
   // being streamed, and this trace shares the CUs with the previous frame's trace or sum
   const bool prev_in_flight = !dry && c->pending && hipEventQuery(c->ev1) == hipErrorNotReady;
+  // an adaptive frame (FR_FLAG_ADAPTIVE) is planned over the context's active tile list; it
+  // fails, or with an empty list ends, here, before anything is enqueued. A dry run plans the
+  // whole shard (the list's upper bound) and reads no state.
+  const bool adaptive = !dry && (p->flags & FR_FLAG_ADAPTIVE) != 0;
+  if (adaptive) {
+    AdaptiveFrame af;
+    if ((rc = adaptive_step(c->accum, c->tiled, accum_key(dc->uid, *cam, *p), &af))) return rc;
+    if (af == AdaptiveFrame::kEmpty) {  // nothing to trace: outputs, A, Q, counts and totals stay
+      c->last = *p;
+      c->last_adaptive = c->last_empty = true;
+      c->last_active_pixels = 0;
+      return FR_OK;
+    }
+  }
   FramePlan fp;
   if ((rc = make_plan(*p, camera_reach(*cam), dc->ps.facts, c->num_cus, c->device_bytes, env, dry,
-                      PlanHistory{prev_in_flight, c->streaming, c->fs_n, c->fs_bytes}, &fp)))
+                      PlanHistory{prev_in_flight, c->streaming, c->fs_n, c->fs_bytes}, &fp,
+                      adaptive ? &c->tiled.active_tiles : nullptr)))
     return rc;
+  if (adaptive) fp.kp.tile_list = c->d_list, fp.kp.flags |= KF_LIST;
   if (!dry) c->streaming = prev_in_flight;
   if (fp.relayout) c->frame_slot = 0;
   const int fs = fp.fpipe ? c->frame_slot % fp.nfs : 0;
@@ -674,6 +713,8 @@ static int render_impl(fr_ctx* c, fr_scene* scene, const fr_camera* cam, const f
     if ((rc = grow_accum(c, fp.running_bytes ? fp.running_bytes : 1u, with_q))) return rc;
     if (!dry && (rc = accum_step(c->accum, accum_key(dc->uid, *cam, *p), p->spp, &step))) return rc;
     acc = SumAccum{c->d_accum, step.start, static_cast<float>(step.next.samples), with_q ? c->d_sq : nullptr};
+    // a tiled accumulation goes on: the resolve takes each tile's own divisor and advances its counts
+    if (!dry && !step.start && c->tiled.tiled) acc.n_t = c->d_nt, acc.k_t = c->d_kt;
   }
   const size_t n_ev = static_cast<size_t>(fp.passes > 0 ? fp.passes : 1);
   if ((rc = grow_events(c->ev_sum, n_ev, hipEventDisableTiming))) return rc;
@@ -690,8 +731,12 @@ static int render_impl(fr_ctx* c, fr_scene* scene, const fr_camera* cam, const f
       return rc;
     if (accumulate) {
       c->accum = step.next;
-      c->accum_kp = fp.kp;
+      if (!adaptive) c->accum_kp = fp.kp;  // the whole shard's constants (an adaptive frame's are its list's)
+      if (step.start) c->tiled = TiledState{};  // a new accumulation is uniform: counts and list are dead
     }
+    c->last_adaptive = adaptive;
+    c->last_empty = false;
+    c->last_active_pixels = adaptive ? c->tiled.active_pixels : 0;
     c->last = *p;
     c->last_n = dc->ps.facts.n;
     c->pending = true;
@@ -707,6 +752,10 @@ int fr_ctx_sync(fr_ctx* c, fr_stats* st) {
   HIPCHK(hipStreamSynchronize(c->stream));
   if (!c->pending) return set_error(FR_EARG, "fr_ctx_sync: nothing rendered");
   HIPCHK(hipEventSynchronize(c->ev1));  // the frame's end (on the sum stream when pipelined)
+  if (st && c->last_empty) {  // an adaptive frame with an empty list: nothing was traced
+    memset(st, 0, sizeof(*st));
+    return FR_OK;
+  }
   if (st) {
     unsigned long long cnt[kCntWords] = {};
     HIPCHK(hipMemcpy(cnt, c->last_cnt, sizeof(cnt), hipMemcpyDeviceToHost));
@@ -776,7 +825,7 @@ int fr_ctx_sync(fr_ctx* c, fr_stats* st) {
     const ShardStrips ss = shard_strips(p.height, p.shard_index, p.shard_count, (p.flags & FR_FLAG_MT_BANDS) != 0);
     st->segments = cnt[0];
     st->hits = cnt[1];
-    st->samples = ss.rows * p.width * static_cast<uint64_t>(p.spp);
+    st->samples = (c->last_adaptive ? c->last_active_pixels : ss.rows * p.width) * static_cast<uint64_t>(p.spp);
     st->prim_tests = cnt[0] * static_cast<uint64_t>(c->last_n);
     st->kernel_ms = ms;
     double tms = 0.0;
@@ -790,7 +839,7 @@ int fr_ctx_sync(fr_ctx* c, fr_stats* st) {
     st->occupancy = static_cast<uint32_t>(c->occupancy);
     // every path traces one segment more than it scatters (tracer.rs:189-210: each scatter
     // is followed by one more get_color), so the kernel counts segments and hits only
-    st->scatters = cnt[0] - ss.traced_rows * p.width * static_cast<uint64_t>(p.spp);
+    st->scatters = cnt[0] - (c->last_adaptive ? c->last_active_pixels : ss.traced_rows * p.width) * static_cast<uint64_t>(p.spp);
     st->total_ms =
         std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - c->t0).count();
   }
@@ -927,6 +976,7 @@ int fr_jit_wait(void) { return jit_wait_all(); }
 int fr_ctx_accum_reset(fr_ctx* c) {
   if (!c) return set_error(FR_EARG, "fr_ctx_accum_reset: null ctx");
   c->accum = AccumState{};  // (host state only: the next accumulating frame's sum overwrites A)
+  c->tiled = TiledState{};  // the counts and the tile list die with the accumulation
   return FR_OK;
 }
 
@@ -961,8 +1011,12 @@ int fr_ctx_accum_error(fr_ctx* c, float threshold, fr_accum_error* out) {
   if ((rc = grow(c->d_err_part, c->cap_err_part, (groups ? groups : 1u) * 2u * sizeof(uint32_t)))) return rc;
   if (!c->d_err_sum) HIPCHK(hipMalloc(&c->d_err_sum, sizeof(ErrSummary)));
   c->err_valid = false;
-  HIPCHK(launch_accum_error(c->stream_sum, kp, c->d_accum, c->d_sq, static_cast<float>(a.samples),
-                            static_cast<float>(a.frames - 1u), threshold, c->d_err, c->d_err_part, c->d_err_sum));
+  if (c->tiled.tiled)  // per-tile n_t and K_t (frames and samples below stay the host's totals)
+    HIPCHK(launch_adapt(c->stream_sum, kp, c->d_accum, c->d_sq, c->d_nt, c->d_kt, threshold, 0u, c->d_err,
+                        c->d_err_part, nullptr, nullptr, nullptr, c->d_err_sum));
+  else
+    HIPCHK(launch_accum_error(c->stream_sum, kp, c->d_accum, c->d_sq, static_cast<float>(a.samples),
+                              static_cast<float>(a.frames - 1u), threshold, c->d_err, c->d_err_part, c->d_err_sum));
   ErrSummary sum{};
   HIPCHK(hipMemcpyAsync(&sum, c->d_err_sum, sizeof(sum), hipMemcpyDeviceToHost, c->stream_sum));
   HIPCHK(hipStreamSynchronize(c->stream_sum));
@@ -975,6 +1029,100 @@ int fr_ctx_accum_error(fr_ctx* c, float threshold, fr_accum_error* out) {
   out->converged = sum.converged;
   memcpy(&out->max_rel, &sum.max_bits, sizeof(float));
   out->threshold = threshold;
+  return FR_OK;
+}
+
+// The selection: like fr_ctx_accum_error on the sum stream, behind every
+// enqueued resolve, and waited for there alone. Each frame's sum follows its trace, so every
+// enqueued trace, the readers of the previous list, has finished when the select kernel runs.
+int fr_ctx_adapt(fr_ctx* c, float threshold, uint32_t min_samples, fr_adapt_info* out) {
+  if (!c || !out) return set_error(FR_EARG, "fr_ctx_adapt: null argument");
+  if (!(threshold >= 0.0f))
+    return set_error(FR_EARG, "fr_ctx_adapt: threshold %g must be >= 0 (+infinity selects by min_samples alone)",
+                     static_cast<double>(threshold));
+  const AccumState& a = c->accum;
+  if (!a.live) return set_error(FR_EARG, "fr_ctx_adapt: no live accumulation (no FR_FLAG_ACCUMULATE frame yet, or reset)");
+  if (!a.has_q || !c->d_sq)
+    return set_error(FR_EARG, "fr_ctx_adapt: the live accumulation carries no Q: its frames lack FR_FLAG_ACCUM_ERROR");
+  if (a.frames < 2)
+    return set_error(FR_EARG, "fr_ctx_adapt: %u frame in the accumulation, the estimate needs two", a.frames);
+  SET_DEVICE(c->device);
+  const KParams& kp = c->accum_kp;
+  const uint32_t groups = (kp.P + kSumThreads - 1u) / kSumThreads;
+  const size_t tile_bytes = (kp.n_tiles ? kp.n_tiles : 1u) * sizeof(uint32_t);
+  int rc;
+  if ((rc = grow(c->d_err, c->cap_err, static_cast<size_t>(kp.W) * kp.H * sizeof(float)))) return rc;
+  if ((rc = grow(c->d_err_part, c->cap_err_part, (groups ? groups : 1u) * 2u * sizeof(uint32_t)))) return rc;
+  if ((rc = grow(c->d_tile_px, c->cap_tile_px, tile_bytes))) return rc;
+  if (!c->d_adapt_sum) HIPCHK(hipMalloc(&c->d_adapt_sum, sizeof(AdaptSummary)));
+  if (!c->tiled.tiled) {
+    // the accumulation becomes tiled: every tile starts from the uniform (n, K). The arrays
+    // may be an earlier, dead accumulation's: its resolves, their last users, are on the sum
+    // stream, which is drained before a larger pair replaces them.
+    HIPCHK(hipStreamSynchronize(c->stream_sum));
+    if ((rc = grow(c->d_nt, c->cap_nt, tile_bytes))) return rc;
+    if ((rc = grow(c->d_kt, c->cap_kt, tile_bytes))) return rc;
+    HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c->d_nt), static_cast<int>(a.samples), kp.n_tiles,
+                             c->stream_sum));
+    HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c->d_kt), static_cast<int>(a.frames), kp.n_tiles,
+                             c->stream_sum));
+  }
+  // The previous list is overwritten in place. Its readers are the traces and sums of the
+  // adaptive frames enqueued so far: the sums are ahead of the select kernel on the sum stream,
+  // and each trace has finished before its frame's sum starts. (A larger list is a new
+  // allocation: the stream is drained first.)
+  if (c->cap_list < tile_bytes) HIPCHK(hipStreamSynchronize(c->stream_sum));
+  if ((rc = grow(c->d_list, c->cap_list, tile_bytes))) return rc;
+  c->err_valid = false;
+  HIPCHK(launch_adapt(c->stream_sum, kp, c->d_accum, c->d_sq, c->d_nt, c->d_kt, threshold, min_samples, c->d_err,
+                      c->d_err_part, c->d_tile_px, c->d_list, c->d_adapt_sum, nullptr));
+  AdaptSummary sum{};
+  HIPCHK(hipMemcpyAsync(&sum, c->d_adapt_sum, sizeof(sum), hipMemcpyDeviceToHost, c->stream_sum));
+  HIPCHK(hipStreamSynchronize(c->stream_sum));
+  c->err_kp = kp;
+  c->err_valid = true;
+  c->tiled.tiled = true;
+  c->tiled.tiles = kp.n_tiles;
+  c->tiled.active_tiles = sum.active_tiles;
+  c->tiled.active_pixels = sum.active_pixels;
+  const ShardStrips ss = shard_strips(kp.H, kp.shard_index, kp.shard_count, false);
+  memset(out, 0, sizeof(*out));
+  out->frames = a.frames;
+  out->samples = a.samples;
+  out->tiles = kp.n_tiles;  // (every tile of a shard starts inside the image)
+  out->active_tiles = sum.active_tiles;
+  out->pixels = ss.rows * kp.W;
+  out->active_pixels = sum.active_pixels;
+  out->converged = sum.converged;
+  memcpy(&out->max_rel, &sum.max_bits, sizeof(float));
+  out->threshold = threshold;
+  out->min_samples = min_samples;
+  return FR_OK;
+}
+
+// The per-tile counts spread over the tiles' pixels on the host (slot_xy's tile order): not a
+// hot path, and the arrays are one uint32 per 64 pixels.
+int fr_ctx_download_counts(fr_ctx* c, uint32_t* samples, uint32_t* frames) {
+  if (!c) return set_error(FR_EARG, "fr_ctx_download_counts: null ctx");
+  const AccumState& a = c->accum;
+  if (!a.live) return set_error(FR_EARG, "fr_ctx_download_counts: no live accumulation");
+  SET_DEVICE(c->device);
+  const KParams& kp = c->accum_kp;
+  std::vector<uint32_t> nt(kp.n_tiles, a.samples), kt(kp.n_tiles, a.frames);
+  if (c->tiled.tiled && kp.n_tiles) {
+    HIPCHK(hipMemcpyAsync(nt.data(), c->d_nt, kp.n_tiles * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream_sum));
+    HIPCHK(hipMemcpyAsync(kt.data(), c->d_kt, kp.n_tiles * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream_sum));
+    HIPCHK(hipStreamSynchronize(c->stream_sum));
+  }
+  for (uint32_t tile = 0; tile < kp.n_tiles; ++tile) {
+    const uint32_t ls = tile / kp.tiles_per_row, tc = tile - ls * kp.tiles_per_row;
+    const uint32_t y0 = (kp.shard_index + ls * kp.shard_count) * kStripRows, x0 = tc * 8u;
+    for (uint32_t y = y0; y < y0 + kStripRows && y < kp.H; ++y)
+      for (uint32_t x = x0; x < x0 + 8u && x < kp.W; ++x) {
+        if (samples) samples[static_cast<size_t>(y) * kp.W + x] = nt[tile];
+        if (frames) frames[static_cast<size_t>(y) * kp.W + x] = kt[tile];
+      }
+  }
   return FR_OK;
 }
 

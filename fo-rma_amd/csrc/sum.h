@@ -20,6 +20,11 @@ struct SumAccum {
   // FR_FLAG_ACCUM_ERROR: Q, indexed like A; the resolve also does Q = S^2 / spp (start) or
   // Q = Q + S^2 / spp per channel (accum_error.h). Null: the frame carries no Q.
   float* sq = nullptr;
+  // A tiled accumulation (fr_ctx_adapt): per shard tile, the samples and frames its pixels
+  // hold. The resolve then divides by the tile's own count and advances both for the frame's
+  // tiles (KParams::tile_list: an adaptive frame's list, else every tile); `divisor` is unused.
+  uint32_t* n_t = nullptr;
+  uint32_t* k_t = nullptr;
 };
 
 // wps: words per sample record (2 or 3); the record's form by KParams flags.

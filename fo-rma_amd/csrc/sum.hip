@@ -65,10 +65,33 @@ __device__ __forceinline__ V3 accum_resolve_sq(uint32_t q, V3 sum, float fspp, f
   return divs(a, divisor);
 }
 
+// The resolve of a frame in a tiled accumulation (fr_ctx_adapt): A and Q at the
+// pixel's real slot (its tile through the frame's list), the divisor from the tile's own
+// sample count n_t, which with the tile's frame count K_t is written back by one lane: a wave
+// is one tile, every lane of it loads the old n_t before the store that depends on it issues,
+// and no other wave of the launch touches the tile. Such a frame never starts an accumulation.
+__device__ __forceinline__ V3 accum_resolve_tiled(const KParams& kp, uint32_t q, V3 sum, float* __restrict__ accum,
+                                                  int, float, float* __restrict__ sq, uint32_t* __restrict__ n_t,
+                                                  uint32_t* __restrict__ k_t) {
+  const uint32_t tile = slot_tile(kp, q);
+  const uint32_t n = n_t[tile] + kp.spp;
+  const V3 mean = accum_resolve_sq((tile << 6) | (q & 63u), sum, static_cast<float>(kp.spp), accum, 0,
+                                   static_cast<float>(n), sq);
+  // the wave's first lane here (slots past the image edge have returned)
+  if (__ffsll(static_cast<long long>(__ballot(1))) - 1 == static_cast<int>(threadIdx.x & 63u)) {
+    n_t[tile] = n;
+    k_t[tile] = k_t[tile] + 1u;
+  }
+  return mean;
+}
+
 // ACC: empty for the plain kernels, which take the arguments they always took and compile to
 // the same code; {float* accum, int start, float divisor} for the accumulating variant, and
 // {float* accum, int start, float divisor, float* sq} for the one that also fills Q
-// (launch_sum). They are arguments of the accumulating kernels alone, not KParams members:
+// (launch_sum); with {uint32_t* n_t, uint32_t* k_t} behind those four, the kernel of a tiled
+// accumulation and of every pass of an adaptive frame: it alone reads KParams::tile_list
+// (`running` is indexed by the frame's compact slot, A and Q by the real one). They are
+// arguments of the accumulating kernels alone, not KParams members:
 // KParams is shared with the trace kernel and the scene-kernel cache key.
 template <uint32_t WPS, class... ACC>
 __global__ __launch_bounds__(kSumThreads) FR_SUM_VGPR_CAP void sum_kernel(KParams kp, const float* __restrict__ samples,
@@ -77,6 +100,7 @@ __global__ __launch_bounds__(kSumThreads) FR_SUM_VGPR_CAP void sum_kernel(KParam
                                                           const float4* __restrict__ att, uint32_t n_prims,
                                                           ACC... acc) {
   constexpr bool kAcc = sizeof...(ACC) != 0;
+  constexpr bool kTiled = sizeof...(ACC) == 6;
   constexpr uint32_t kSumSlot = WPS * kBlockSamples + 1;  // floats per slot in LDS (odd stride)
   // one LDS block, the attenuation table first: its entries then sit at LDS byte offset
   // 12 x index, and the per-level reads need no base-address add (the table behind the
@@ -106,7 +130,7 @@ __global__ __launch_bounds__(kSumThreads) FR_SUM_VGPR_CAP void sum_kernel(KParam
   const uint32_t q0 = blockIdx.x * kSumThreads, q = q0 + t;
   const uint32_t nq = min(kSumThreads, kp.P - q0);
   uint32_t x = 0, y = 0;
-  const bool valid = q < kp.P && slot_xy(kp, q, x, y);
+  const bool valid = q < kp.P && slot_xy<kTiled>(kp, q, x, y);
   const bool mt = !kAcc && (kp.flags & FR_FLAG_MT_BANDS) != 0;  // (save_image_mt never accumulates: FR_EARG)
   const bool mt_zero = mt && !(kp.band_h && y / kp.band_h < 4u);  // rows render_mt never fills stay 0
   V3 sum = (first || !valid) ? V3{0.0f, 0.0f, 0.0f} : V3{running[3 * q], running[3 * q + 1], running[3 * q + 2]};
@@ -228,7 +252,9 @@ __global__ __launch_bounds__(kSumThreads) FR_SUM_VGPR_CAP void sum_kernel(KParam
     return;
   }
   V3 mean;
-  if constexpr (sizeof...(ACC) == 4)
+  if constexpr (kTiled)
+    mean = accum_resolve_tiled(kp, q, sum, acc...);
+  else if constexpr (sizeof...(ACC) == 4)
     mean = accum_resolve_sq(q, sum, static_cast<float>(kp.spp), acc...);
   else if constexpr (kAcc)
     mean = accum_resolve(q, sum, acc...);
@@ -256,6 +282,7 @@ __global__ __launch_bounds__(kSumThreads) FR_SUM_VGPR_CAP void sum_nib_kernel(
     uint8_t* __restrict__ out_u8, int first, int last, const float4* __restrict__ att, uint32_t n_prims,
     ACC... acc) {
   constexpr bool kAcc = sizeof...(ACC) != 0;
+  constexpr bool kTiled = sizeof...(ACC) == 6;
   __shared__ float4 att16[16];  // level k's entry at byte 16 x nibble (15: the unit entry)
   const uint32_t t = threadIdx.x;
   if (t < 16u) {
@@ -265,7 +292,7 @@ __global__ __launch_bounds__(kSumThreads) FR_SUM_VGPR_CAP void sum_nib_kernel(
   const uint32_t q0 = blockIdx.x * kSumThreads, q = q0 + t;
   const uint32_t nq = min(kSumThreads, kp.P - q0);
   uint32_t x = 0, y = 0;
-  const bool valid = q < kp.P && slot_xy(kp, q, x, y);
+  const bool valid = q < kp.P && slot_xy<kTiled>(kp, q, x, y);
   V3 sum = (first || !valid) ? V3{0.0f, 0.0f, 0.0f} : V3{running[3 * q], running[3 * q + 1], running[3 * q + 2]};
   asm volatile("" : "+v"(sum.x), "+v"(sum.y), "+v"(sum.z));
   __syncthreads();
@@ -321,7 +348,9 @@ __global__ __launch_bounds__(kSumThreads) FR_SUM_VGPR_CAP void sum_nib_kernel(
   }
   const size_t idx = (static_cast<size_t>(y) * kp.W + x) * 3u;
   V3 mean;
-  if constexpr (sizeof...(ACC) == 4)
+  if constexpr (kTiled)
+    mean = accum_resolve_tiled(kp, q, sum, acc...);
+  else if constexpr (sizeof...(ACC) == 4)
     mean = accum_resolve_sq(q, sum, static_cast<float>(kp.spp), acc...);
   else if constexpr (kAcc)
     mean = accum_resolve(q, sum, acc...);
@@ -342,7 +371,26 @@ hipError_t launch_sum(uint32_t wps, uint32_t blocks, hipStream_t stream, const K
                       const float4* att, uint32_t n_prims, const SumAccum* acc) {
   const dim3 grid(blocks), block(kSumThreads);
   const bool nib = wps == 2 && kp.ks == kBlockSamples && !(kp.flags & FR_FLAG_MT_BANDS);
-  if (acc && last) {  // only a frame's last pass resolves; earlier passes run the plain kernels
+  if (acc && acc->n_t && (last || kp.tile_list)) {
+    // a tiled accumulation: the last pass resolves per tile; an adaptive frame's earlier passes
+    // run this kernel too, the only sum that maps compact slots through the list
+    if (!acc->accum || !acc->sq || !acc->k_t || acc->start || (kp.flags & FR_FLAG_MT_BANDS))
+      return hipErrorInvalidValue;
+    if (nib)
+      hipLaunchKernelGGL((sum_nib_kernel<float*, int, float, float*, uint32_t*, uint32_t*>), grid, block, 0, stream, kp,
+                         samples, running, out_mean, out_u8, first, last, att, n_prims, acc->accum, 0, acc->divisor,
+                         acc->sq, acc->n_t, acc->k_t);
+    else if (wps == 2)
+      hipLaunchKernelGGL((sum_kernel<2, float*, int, float, float*, uint32_t*, uint32_t*>), grid, block, 0, stream, kp,
+                         samples, running, out_mean, out_u8, first, last, att, n_prims, acc->accum, 0, acc->divisor,
+                         acc->sq, acc->n_t, acc->k_t);
+    else
+      hipLaunchKernelGGL((sum_kernel<3, float*, int, float, float*, uint32_t*, uint32_t*>), grid, block, 0, stream, kp,
+                         samples, running, out_mean, out_u8, first, last, att, n_prims, acc->accum, 0, acc->divisor,
+                         acc->sq, acc->n_t, acc->k_t);
+  } else if (kp.tile_list) {
+    return hipErrorInvalidValue;  // an adaptive frame outside a tiled accumulation
+  } else if (acc && last) {  // only a frame's last pass resolves; earlier passes run the plain kernels
     if (!acc->accum || (kp.flags & FR_FLAG_MT_BANDS)) return hipErrorInvalidValue;
     const int start = acc->start ? 1 : 0;
     if (acc->sq) {  // FR_FLAG_ACCUM_ERROR: the instantiations that also fill Q

@@ -262,11 +262,25 @@ __device__ __forceinline__ uint32_t lane_sel(unsigned long long m, uint32_t if_s
 #endif
 }
 
+// The shard's real tile of slot q: q >> 6, or for an adaptive frame (KParams::tile_list) the
+// list's entry for the compact tile. Every caller's wave covers one tile (a batch, a sum wave
+// and an error wave are 64 consecutive slots from a multiple of 64), so the index is uniform
+// and the entry comes by one scalar load.
+__device__ __forceinline__ uint32_t slot_tile(const KParams& kp, uint32_t q) {
+  uint32_t tile = q >> 6;
+#if defined(__HIP_DEVICE_COMPILE__)
+  if (kp.flags & KF_LIST) tile = kp.tile_list[__builtin_amdgcn_readfirstlane(tile)];
+#endif
+  return tile;
+}
+
 // Pixel slot q of a shard -> image coordinates. Slots run tile by tile (8x8 pixels,
 // tiles left to right within an 8-row strip, the shard's strips top to bottom); slots
-// past the image edge are invalid.
+// past the image edge are invalid. LIST = false: for kernels that never run an adaptive
+// frame (the plain and untiled accumulating sums), which then read no tile list.
+template <bool LIST = true>
 __device__ __forceinline__ bool slot_xy(const KParams& kp, uint32_t q, uint32_t& x, uint32_t& y) {
-  const uint32_t tile = q >> 6, l = q & 63u;
+  const uint32_t tile = LIST ? slot_tile(kp, q) : q >> 6, l = q & 63u;
   const uint32_t ls = fastdiv(tile, kp.row_magic, kp.row_shift);  // tile / tiles_per_row
   const uint32_t tc = tile - ls * kp.tiles_per_row;
   const uint32_t strip = kp.shard_index + ls * kp.shard_count;

@@ -39,6 +39,8 @@ FR_FLAG_SCENE_JIT_CACHED = 16  # ... only when already built or on disk; never c
 FR_FLAG_ACCUMULATE = 32  # the frame's sum joins the context's accumulator; outputs show the running mean
 # with FR_FLAG_ACCUMULATE: the accumulation also carries Q (sum of S^2 / spp), for accum_error()
 FR_FLAG_ACCUM_ERROR = 64
+# with both: the frame traces only the tiles of the context's active tile list (RenderContext.adapt)
+FR_FLAG_ADAPTIVE = 128
 FR_ERR_FLOOR = 2.0 ** -7  # the relative error's smallest denominator (forma_rt.h)
 FR_JIT_OFF, FR_JIT_USED, FR_JIT_PENDING, FR_JIT_FAILED, FR_JIT_MISS = 0, 1, 2, 3, 4  # fr_ctx_jit_state
 MAX_DEPTH = 50  # tracer.rs:10
@@ -91,6 +93,15 @@ class FrAccumError(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class FrAdaptInfo(C.Structure):
+    _fields_ = [("frames", C.c_uint32), ("samples", C.c_uint32), ("tiles", C.c_uint32), ("active_tiles", C.c_uint32),
+                ("pixels", C.c_uint64), ("active_pixels", C.c_uint64), ("converged", C.c_uint64),
+                ("max_rel", C.c_float), ("threshold", C.c_float), ("min_samples", C.c_uint32), ("pad", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
+
+
 # Every symbol include/forma_rt.h declares (checked by tests/test_abi.py).
 EXPORTS = (
     "fr_last_error", "fr_abi_version", "fr_device_count",
@@ -107,6 +118,7 @@ EXPORTS = (
     "fr_ctx_prepare", "fr_ctx_jit_state", "fr_jit_wait",
     "fr_ctx_accum_reset", "fr_ctx_accum_info", "fr_mctx_accum_reset", "fr_mctx_accum_info",
     "fr_ctx_accum_error", "fr_ctx_download_error", "fr_mctx_accum_error",
+    "fr_ctx_adapt", "fr_ctx_download_counts", "fr_mctx_adapt",
 )
 
 _lib = None
@@ -208,6 +220,10 @@ def lib():
         L.fr_ctx_accum_error.argtypes = [vp, C.c_float, P(FrAccumError)]
         L.fr_ctx_download_error.argtypes = [vp, f3]
         L.fr_mctx_accum_error.argtypes = [vp, C.c_float, P(FrAccumError), f3]
+    if hasattr(L, "fr_ctx_adapt"):  # absent from A/B builds of older sources
+        L.fr_ctx_adapt.argtypes = [vp, C.c_float, C.c_uint32, P(FrAdaptInfo)]
+        L.fr_ctx_download_counts.argtypes = [vp, P(C.c_uint32), P(C.c_uint32)]
+        L.fr_mctx_adapt.argtypes = [vp, C.c_float, C.c_uint32, P(FrAdaptInfo)]
     _lib = L
     return L
 
@@ -435,14 +451,17 @@ def make_params(width, height, spp, max_depth=MAX_DEPTH, seed=DEFAULT_SEED, shar
     "cached" (the scene kernel only if already built or on disk; never a compile).
     accumulate: FR_FLAG_ACCUMULATE, the frame refines the context's accumulation of this view
     (forma_rt.h); give every frame its own seed. accumulate="error": FR_FLAG_ACCUM_ERROR as
-    well, the accumulation carries what accum_error() needs (same picture)."""
+    well, the accumulation carries what accum_error() needs (same picture).
+    accumulate="adaptive": FR_FLAG_ADAPTIVE on top of both, the frame traces only the tiles of
+    the context's active tile list (RenderContext.adapt) and leaves every other pixel as it is."""
     p = FrParams()
     p.width, p.height, p.spp, p.max_depth, p.seed = width, height, spp, max_depth, seed
     p.strip_rows, p.shard_index, p.shard_count = 8, shard_index, shard_count
     p.flags = ((FR_FLAG_WRITE_U8 if write_u8 else 0) | (FR_FLAG_MT_BANDS if mt_bands else 0) |
                (FR_FLAG_SCENE_JIT if scene_jit else 0) | (FR_FLAG_SCENE_JIT_WAIT if scene_jit == "wait" else 0) |
                (FR_FLAG_SCENE_JIT_CACHED if scene_jit == "cached" else 0) | (FR_FLAG_ACCUMULATE if accumulate else 0) |
-               (FR_FLAG_ACCUM_ERROR if isinstance(accumulate, str) and accumulate == "error" else 0))
+               (FR_FLAG_ACCUM_ERROR if isinstance(accumulate, str) and accumulate in ("error", "adaptive") else 0) |
+               (FR_FLAG_ADAPTIVE if isinstance(accumulate, str) and accumulate == "adaptive" else 0))
     return p
 
 
@@ -587,6 +606,30 @@ class RenderContext:
         check(lib().fr_ctx_download_error(self._h, rel.ctypes.data_as(C.POINTER(C.c_float))))
         return rel
 
+    def adapt(self, threshold, min_samples=0):
+        """Builds the context's active tile list from the error estimate of the live
+        accumulation (fr_ctx_adapt): an 8x8 tile is active iff one of its pixels has a relative
+        standard error > threshold or the tile holds fewer than min_samples samples per pixel.
+        Frames of make_params(accumulate="adaptive") then trace those tiles only. A dict of
+        frames, samples, tiles, active_tiles, pixels, active_pixels, converged, max_rel,
+        threshold and min_samples. Waits for the frames enqueued so far; download_error() gives
+        the map it used, download_counts() the per-pixel sample counts."""
+        e = FrAdaptInfo()
+        check(lib().fr_ctx_adapt(self._h, float(threshold), int(min_samples), C.byref(e)))
+        return e.as_dict()
+
+    def download_counts(self, samples=None, frames=None):
+        """(samples, frames): the per-pixel sample and frame counts of the live accumulation as
+        [H, W] uint32, this shard's rows written into the arrays given (new zero-filled ones
+        when None; the shape is the last accumulating frame's)."""
+        if samples is None:
+            samples = np.zeros(self._err_shape(), dtype=np.uint32)
+        if frames is None:
+            frames = np.zeros(self._err_shape(), dtype=np.uint32)
+        check(lib().fr_ctx_download_counts(self._h, samples.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                           frames.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return samples, frames
+
     def _err_shape(self):
         shape = getattr(self, "_accum_shape", None)
         if shape is None:
@@ -694,6 +737,13 @@ class MultiContext:
                                         rel.ctypes.data_as(C.POINTER(C.c_float)) if want_map else None))
         return (e.as_dict(), rel) if want_map else e.as_dict()
 
+    def adapt(self, threshold, min_samples=0):
+        """RenderContext.adapt over every shard: the counts are the shards' sums, max_rel their
+        maximum, frames and samples the largest of the shards'."""
+        e = FrAdaptInfo()
+        check(lib().fr_mctx_adapt(self._h, float(threshold), int(min_samples), C.byref(e)))
+        return e.as_dict()
+
     def context(self, i):
         """The i-th shard's RenderContext view (not owned: do not close it)."""
         h = C.c_void_p()
@@ -715,22 +765,41 @@ class MultiContext:
 
 
 def render_converged(ctx, scene, cam, w, h, spp, max_depth, seed, target, fraction=1.0, max_frames=64, check_every=1,
-                     scene_jit=False):
+                     scene_jit=False, adaptive=False, min_samples=0):
     """Accumulating frames of `spp` samples on `ctx` (frame k = 1, 2, ... has seed `seed + k`)
     until, at a checked frame k >= 2 (every check_every-th), converged >= fraction * pixels for
     the relative standard error `target` (accum_error), or max_frames are done. Starts a new
     accumulation. Returns (mean[H,W,3] f32, u8[H,W,3], the last summary, or None if none was
-    taken)."""
+    taken).
+    adaptive: the check is adapt(target, min_samples) and the frames after it trace only the
+    tiles it found active; it also stops when no tile is active. The summary is then adapt()'s,
+    with "traced": the samples traced in all frames (the sum of their stats' samples; a uniform
+    run traces pixels * samples)."""
     ctx.accum_reset()
     summary = None
+    mode = "error"
+    uniform_frames, traced, per_frame = 0, 0, None  # per_frame: samples an adaptive frame traces
     for k in range(1, max_frames + 1):
-        ctx.render(scene, cam, make_params(w, h, spp, max_depth, seed + k, accumulate="error", scene_jit=scene_jit))
+        ctx.render(scene, cam, make_params(w, h, spp, max_depth, seed + k, accumulate=mode, scene_jit=scene_jit))
+        if per_frame is None:
+            uniform_frames += 1
+        else:
+            traced += per_frame
         if k >= 2 and k % check_every == 0:
-            summary = ctx.accum_error(target)
+            if adaptive:
+                summary = ctx.adapt(target, min_samples)
+                mode = "adaptive"
+                per_frame = summary["active_pixels"] * spp
+                if summary["active_tiles"] == 0:
+                    break
+            else:
+                summary = ctx.accum_error(target)
             if summary["converged"] >= fraction * summary["pixels"]:
                 break
     ctx.sync()
     mean, u8 = ctx.download(w, h)
+    if adaptive and summary is not None:
+        summary["traced"] = traced + uniform_frames * summary["pixels"] * spp
     return mean, u8, summary
 
 

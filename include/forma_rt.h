@@ -59,7 +59,9 @@ extern "C" {
                                FR_FLAG_SCENE_JIT_WAIT, fr_ctx_jit_state, fr_jit_wait
                                (still 6, additive: FR_FLAG_ACCUMULATE, fr_ctx_accum_reset / _info,
                                fr_mctx_accum_reset / _info; FR_FLAG_ACCUM_ERROR,
-                               fr_ctx_accum_error, fr_ctx_download_error, fr_mctx_accum_error) */
+                               fr_ctx_accum_error, fr_ctx_download_error, fr_mctx_accum_error;
+                               FR_FLAG_ADAPTIVE, fr_adapt_info, fr_ctx_adapt, fr_ctx_download_counts,
+                               fr_mctx_adapt) */
 
 /* error codes */
 #define FR_OK 0
@@ -148,6 +150,28 @@ extern "C" {
    2^-12 sqrt(K) reads as 0 or as noise of that size, far under one u8 step. */
 #define FR_FLAG_ACCUM_ERROR 64u
 #define FR_ERR_FLOOR 0.0078125f /* 2^-7 */
+/* Adaptive sampling, with FR_FLAG_ACCUMULATE | FR_FLAG_ACCUM_ERROR only (FR_EARG without either):
+   the frame traces and resolves only the 8x8 tiles of the context's active tile list, which
+   fr_ctx_adapt builds from the error estimate. The granularity is the tile of a shard in the
+   trace kernel's own order (tile = pixel slot >> 6: tiles left to right within an 8-row strip,
+   the shard's strips top to bottom). For the pixels of the list's tiles the frame does what the
+   accumulating frame does, with the tile's own counts: A += S, Q += S^2 / spp, n_t += spp,
+   K_t += 1, mean = A / (float)n_t, u8 from that mean, in FR_FLAG_ACCUMULATE's and
+   FR_FLAG_ACCUM_ERROR's operation order; S is bit for bit what the plain frame of the same
+   parameters and seed sums for that pixel (a pixel's random streams depend on the seed, its
+   index in the image and the sample block alone). A, Q, the counts and the output buffers of
+   every other pixel are left exactly as they are: a plain render on the same context in
+   between leaves its own values in the inactive tiles of the outputs, where they stay.
+   FR_EARG, before anything is enqueued, when the frame would start a new accumulation and when
+   the live accumulation is not tiled (no fr_ctx_adapt since it started). An empty list is not
+   an error: nothing is traced, outputs and state are untouched and the accumulation's frames
+   and samples do not move. fr_stats.samples = (image pixels in the list's tiles) x spp;
+   segments, hits and prim_tests count what was traced. A frame without this flag in a tiled
+   accumulation is the adaptive frame whose list is every tile; the two kinds mix freely (the
+   flag is not part of what a frame must share to continue an accumulation). FR_EARG through
+   fr_render_hip / fr_render_hip_multi, as FR_FLAG_ACCUMULATE. fr_ctx_prepare with the flag
+   allocates (for the whole shard) and changes no state. */
+#define FR_FLAG_ADAPTIVE 128u
 /* fr_ctx_jit_state: which trace kernel the last render (or fr_ctx_prepare) ran */
 #define FR_JIT_OFF 0     /* compiled-in kernel: not asked for, a BVH scene, or > 64 primitives */
 #define FR_JIT_USED 1    /* the scene-specialised kernel */
@@ -319,6 +343,32 @@ int fr_ctx_accum_error(fr_ctx* ctx, float threshold, fr_accum_error* out);
 /* Copies the map of the last fr_ctx_accum_error into rel (W x H f32, row-major): this shard's
    rows only, the others are left untouched. */
 int fr_ctx_download_error(fr_ctx* ctx, float* rel);
+/* Adaptive sampling (FR_FLAG_ADAPTIVE): the selection's summary. */
+typedef struct fr_adapt_info {  /* 56 bytes */
+  uint32_t frames, samples;     /* frames enqueued in the accumulation; sum of their spp (the largest per-tile n possible) */
+  uint32_t tiles, active_tiles; /* tiles of the shard(s) with at least one pixel in the image; of them, in the list */
+  uint64_t pixels, active_pixels; /* image pixels of the shard(s); of them, in active tiles */
+  uint64_t converged;           /* pixels with rel <= threshold (as fr_accum_error.converged) */
+  float max_rel, threshold;
+  uint32_t min_samples, pad;    /* pad = 0 */
+} fr_adapt_info;
+/* Computes rel for every pixel of the shard as fr_ctx_accum_error does, with the pixel's tile's
+   own n_t and K_t for n and K, into the map fr_ctx_download_error reads, and builds the
+   context's active tile list, in ascending tile order: a tile is active iff the maximum of rel
+   over its image pixels is > threshold (compared as uint32 bits) or its n_t < min_samples. The
+   same conditions and FR_EARGs as fr_ctx_accum_error; like it, it runs behind every enqueued
+   frame's resolve and waits for that alone. The first successful call makes the live
+   accumulation tiled: n_t and K_t start from its uniform (n, K) and every later frame's
+   resolve maintains them; they and the list die with the accumulation (fr_ctx_accum_reset, or
+   a frame that starts a new one), and a new accumulation is uniform until the next call. For a
+   given accumulation the result is the same bits every time, so a tile that was inactive stays
+   inactive under the same threshold. On a tiled accumulation fr_ctx_accum_error uses n_t and
+   K_t too; its frames and samples, and fr_ctx_accum_info's, are the totals given here. */
+int fr_ctx_adapt(fr_ctx* ctx, float threshold, uint32_t min_samples, fr_adapt_info* out);
+/* The per-pixel sample and frame counts of the live accumulation (each pixel's tile's n_t and
+   K_t; the uniform n and K while it is not tiled): W x H uint32 each, either may be NULL; this
+   shard's rows only. Waits for the enqueued resolves. FR_EARG without a live accumulation. */
+int fr_ctx_download_counts(fr_ctx* ctx, uint32_t* samples, uint32_t* frames);
 
 /* ---- persistent multi-device context (tracer.rs:83-134 render_mt, one device per shard) ----
    Entry i of `devices` renders row shard i of n of every frame on its own fr_ctx (device
@@ -346,6 +396,10 @@ int fr_mctx_accum_info(fr_mctx* mctx, uint32_t* frames, uint32_t* samples);
 /* fr_ctx_accum_error on every shard: pixels and converged are the shards' sums, max_rel their
    maximum, frames and samples shard 0's. rel, when not NULL, receives the whole W x H map. */
 int fr_mctx_accum_error(fr_mctx* mctx, float threshold, fr_accum_error* out, float* rel /* or NULL */);
+/* FR_FLAG_ADAPTIVE passes through fr_mctx_render. fr_ctx_adapt on every shard: the counts are
+   the shards' sums, max_rel their maximum, frames and samples the largest of the shards' (a
+   shard whose list was empty did not advance). */
+int fr_mctx_adapt(fr_mctx* mctx, float threshold, uint32_t min_samples, fr_adapt_info* out);
 
 /* Page-locked host memory (hipHostMalloc) for fr_ctx_download_async targets. */
 int fr_host_alloc(size_t bytes, void** out);
