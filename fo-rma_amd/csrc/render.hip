@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "accum_error.h"
+#include "denoise.h"
 #include "hipchk.h"
 #include "jit.h"
 #include "pack.h"
@@ -194,6 +195,16 @@ struct fr_ctx {
   AdaptSummary* d_adapt_sum = nullptr;
   size_t cap_nt = 0, cap_kt = 0, cap_list = 0, cap_tile_px = 0;
   TiledState tiled;
+  // fr_ctx_denoise: the ping and pong pixel buffers and the three outputs,
+  // allocated on first use and kept while the image size is unchanged. dn_valid: a denoise was
+  // enqueued since they were (re)allocated.
+  DnPixel* d_dn_ping = nullptr;
+  DnPixel* d_dn_pong = nullptr;
+  float* d_dn_mean = nullptr;
+  uint8_t* d_dn_u8 = nullptr;
+  float* d_dn_var = nullptr;
+  uint32_t dn_w = 0, dn_h = 0;
+  bool dn_valid = false;
   // the last render was adaptive: the image pixels it traced (fr_stats), or none (empty list)
   bool last_adaptive = false, last_empty = false;
   uint64_t last_active_pixels = 0;
@@ -525,7 +536,9 @@ void fr_ctx_free(fr_ctx* c) {
                   static_cast<void*>(c->d_accum), static_cast<void*>(c->d_sq), static_cast<void*>(c->d_err),
                   static_cast<void*>(c->d_err_part), static_cast<void*>(c->d_err_sum), static_cast<void*>(c->d_nt),
                   static_cast<void*>(c->d_kt), static_cast<void*>(c->d_list), static_cast<void*>(c->d_tile_px),
-                  static_cast<void*>(c->d_adapt_sum)})
+                  static_cast<void*>(c->d_adapt_sum), static_cast<void*>(c->d_dn_ping),
+                  static_cast<void*>(c->d_dn_pong), static_cast<void*>(c->d_dn_mean), static_cast<void*>(c->d_dn_u8),
+                  static_cast<void*>(c->d_dn_var)})
     if (d) (void)hipFree(d);
   for (hipEvent_t e : {c->ev0, c->ev1, c->ev_start, c->ev_copy})
     if (e) (void)hipEventDestroy(e);
@@ -1097,6 +1110,73 @@ int fr_ctx_adapt(fr_ctx* c, float threshold, uint32_t min_samples, fr_adapt_info
   memcpy(&out->max_rel, &sum.max_bits, sizeof(float));
   out->threshold = threshold;
   out->min_samples = min_samples;
+  return FR_OK;
+}
+
+// The filter on demand. Like fr_ctx_accum_error's kernels, prep and the levels
+// go on the sum stream, behind the resolve of every frame enqueued so far and ahead of every
+// later one; unlike it nothing is waited for. A, Q, the counts, d_mean, d_u8, the pending
+// render and its stats are read or untouched: the results have buffers of their own.
+int fr_ctx_denoise(fr_ctx* c, uint32_t levels, float k) {
+  if (!c) return set_error(FR_EARG, "fr_ctx_denoise: null ctx");
+  if (levels < 1u || levels > kDnLevelsMax)
+    return set_error(FR_EARG, "fr_ctx_denoise: levels %u must be 1 to %u", levels, kDnLevelsMax);
+  if (!(k > 0.0f && k <= kDnKMax))
+    return set_error(FR_EARG, "fr_ctx_denoise: k %g must be finite, > 0 and <= %g", static_cast<double>(k),
+                     static_cast<double>(kDnKMax));
+  const AccumState& a = c->accum;
+  if (!a.live) return set_error(FR_EARG, "fr_ctx_denoise: no live accumulation (no FR_FLAG_ACCUMULATE frame yet, or reset)");
+  if (!a.has_q || !c->d_sq)
+    return set_error(FR_EARG, "fr_ctx_denoise: the live accumulation carries no Q: its frames lack FR_FLAG_ACCUM_ERROR");
+  if (a.frames < 2)
+    return set_error(FR_EARG, "fr_ctx_denoise: %u frame in the accumulation, the variance needs two", a.frames);
+  const KParams& kp = c->accum_kp;
+  if (kp.shard_count != 1)
+    return set_error(FR_EARG, "fr_ctx_denoise: shard_count %u: the filter's taps cross the strips of other shards, "
+                              "only a whole image (shard_count 1) is filtered", kp.shard_count);
+  SET_DEVICE(c->device);
+  if (c->dn_w != kp.W || c->dn_h != kp.H || !c->d_dn_var) {
+    // another size: the kernels and copies that use the old buffers are on the sum stream
+    HIPCHK(hipStreamSynchronize(c->stream_sum));
+    c->dn_valid = false;
+    c->dn_w = c->dn_h = 0;
+    const size_t px = static_cast<size_t>(kp.W) * kp.H;
+    size_t caps[5] = {};  // (grow with no capacity: each buffer is replaced)
+    int rc;
+    if ((rc = grow(c->d_dn_ping, caps[0], px * sizeof(DnPixel)))) return rc;
+    if ((rc = grow(c->d_dn_pong, caps[1], px * sizeof(DnPixel)))) return rc;
+    if ((rc = grow(c->d_dn_mean, caps[2], px * 3 * sizeof(float)))) return rc;
+    if ((rc = grow(c->d_dn_u8, caps[3], px * 3))) return rc;
+    if ((rc = grow(c->d_dn_var, caps[4], px * sizeof(float)))) return rc;
+    c->dn_w = kp.W;
+    c->dn_h = kp.H;
+  }
+  const bool tiled = c->tiled.tiled;
+  HIPCHK(launch_denoise(c->stream_sum, kp, c->d_accum, c->d_sq, tiled ? c->d_nt : nullptr, tiled ? c->d_kt : nullptr,
+                        a.samples, a.frames, levels, k, c->d_dn_ping, c->d_dn_pong, c->d_dn_mean, c->d_dn_u8,
+                        c->d_dn_var));
+  c->dn_valid = true;
+  return FR_OK;
+}
+
+int fr_ctx_download_denoised(fr_ctx* c, float* mean_rgb, uint8_t* rgb8, float* var) {
+  if (!c) return set_error(FR_EARG, "fr_ctx_download_denoised: null ctx");
+  if (!c->dn_valid) return set_error(FR_EARG, "fr_ctx_download_denoised: no denoised image (fr_ctx_denoise first)");
+  SET_DEVICE(c->device);
+  const size_t px = static_cast<size_t>(c->dn_w) * c->dn_h;
+  hipStream_t st = c->stream_sum;
+  if (mean_rgb && px) HIPCHK(hipMemcpyAsync(mean_rgb, c->d_dn_mean, px * 3 * sizeof(float), hipMemcpyDeviceToHost, st));
+  if (rgb8 && px) HIPCHK(hipMemcpyAsync(rgb8, c->d_dn_u8, px * 3, hipMemcpyDeviceToHost, st));
+  if (var && px) HIPCHK(hipMemcpyAsync(var, c->d_dn_var, px * sizeof(float), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return FR_OK;
+}
+
+int fr_ctx_denoised_buffers(fr_ctx* c, float** d_mean_rgb, uint8_t** d_rgb8) {
+  if (!c) return set_error(FR_EARG, "fr_ctx_denoised_buffers: null ctx");
+  if (!c->dn_valid) return set_error(FR_EARG, "fr_ctx_denoised_buffers: no denoised image (fr_ctx_denoise first)");
+  if (d_mean_rgb) *d_mean_rgb = c->d_dn_mean;
+  if (d_rgb8) *d_rgb8 = c->d_dn_u8;
   return FR_OK;
 }
 

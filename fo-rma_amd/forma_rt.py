@@ -42,6 +42,9 @@ FR_FLAG_ACCUM_ERROR = 64
 # with both: the frame traces only the tiles of the context's active tile list (RenderContext.adapt)
 FR_FLAG_ADAPTIVE = 128
 FR_ERR_FLOOR = 2.0 ** -7  # the relative error's smallest denominator (forma_rt.h)
+# fr_ctx_denoise (forma_rt.h): the defaults, the edge-stopping floor and the validity caps
+FR_DN_LEVELS_DEFAULT, FR_DN_K_DEFAULT = 4, 4.0
+FR_DN_EPS, FR_DN_MEAN_MAX, FR_DN_VAR_MAX = 2.0 ** -20, 2.0 ** 40, 2.0 ** 80
 FR_JIT_OFF, FR_JIT_USED, FR_JIT_PENDING, FR_JIT_FAILED, FR_JIT_MISS = 0, 1, 2, 3, 4  # fr_ctx_jit_state
 MAX_DEPTH = 50  # tracer.rs:10
 DEFAULT_SEED = 0x5EED
@@ -119,6 +122,7 @@ EXPORTS = (
     "fr_ctx_accum_reset", "fr_ctx_accum_info", "fr_mctx_accum_reset", "fr_mctx_accum_info",
     "fr_ctx_accum_error", "fr_ctx_download_error", "fr_mctx_accum_error",
     "fr_ctx_adapt", "fr_ctx_download_counts", "fr_mctx_adapt",
+    "fr_ctx_denoise", "fr_ctx_download_denoised", "fr_ctx_denoised_buffers",
 )
 
 _lib = None
@@ -224,6 +228,10 @@ def lib():
         L.fr_ctx_adapt.argtypes = [vp, C.c_float, C.c_uint32, P(FrAdaptInfo)]
         L.fr_ctx_download_counts.argtypes = [vp, P(C.c_uint32), P(C.c_uint32)]
         L.fr_mctx_adapt.argtypes = [vp, C.c_float, C.c_uint32, P(FrAdaptInfo)]
+    if hasattr(L, "fr_ctx_denoise"):  # absent from A/B builds of older sources
+        L.fr_ctx_denoise.argtypes = [vp, C.c_uint32, C.c_float]
+        L.fr_ctx_download_denoised.argtypes = [vp, f3, P(C.c_uint8), f3]
+        L.fr_ctx_denoised_buffers.argtypes = [vp, P(vp), P(vp)]
     _lib = L
     return L
 
@@ -630,6 +638,37 @@ class RenderContext:
                                            frames.ctypes.data_as(C.POINTER(C.c_uint32))))
         return samples, frames
 
+    def denoise(self, levels=FR_DN_LEVELS_DEFAULT, k=FR_DN_K_DEFAULT):
+        """Enqueues the variance-guided filter of the live accumulation (fr_ctx_denoise: frames
+        of make_params(accumulate="error") or "adaptive", two or more, shard_count 1) and
+        returns at once: `levels` a-trous levels (1 to 6, steps 1, 2, 4, ...) with edge-stopping
+        scale k (0 < k <= 1024). The result describes the accumulation as of the call;
+        download_denoised() waits for it. The frames' own outputs are untouched."""
+        check(lib().fr_ctx_denoise(self._h, int(levels), float(k)))
+
+    def download_denoised(self, width, height, want_var=False):
+        """(mean [H, W, 3] f32, u8 [H, W, 3]) of the last denoise(), with want_var also the
+        [H, W] f32 variance map the filter steered by (not an error estimate of the filtered
+        picture). Waits for it."""
+        mean = np.full((height, width, 3), np.nan, dtype=np.float32)
+        u8 = np.zeros((height, width, 3), dtype=np.uint8)
+        var = np.full((height, width), np.nan, dtype=np.float32) if want_var else None
+        check(lib().fr_ctx_download_denoised(self._h, mean.ctypes.data_as(C.POINTER(C.c_float)),
+                                             u8.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                             var.ctypes.data_as(C.POINTER(C.c_float)) if want_var else None))
+        return (mean, u8, var) if want_var else (mean, u8)
+
+    def download_denoised_into(self, u8):
+        """Copy the last denoise()'s u8 image into a caller-owned [H, W, 3] array (page-locked
+        arrays copy by DMA). Waits for it."""
+        check(lib().fr_ctx_download_denoised(self._h, None, u8.ctypes.data_as(C.POINTER(C.c_uint8)), None))
+
+    def denoised_buffers(self):
+        """(d_mean_rgb, d_rgb8) device addresses of the last denoise()'s mean and u8 image."""
+        dm, du = C.c_void_p(), C.c_void_p()
+        check(lib().fr_ctx_denoised_buffers(self._h, C.byref(dm), C.byref(du)))
+        return dm.value, du.value
+
     def _err_shape(self):
         shape = getattr(self, "_accum_shape", None)
         if shape is None:
@@ -876,21 +915,31 @@ class TraceModel:
         mean, u8 = ctx.download(self.width, self.height)
         return mean, u8, self.last_stats
 
-    def frame_u8(self, scene, max_depth, seed, accumulate=False):
+    def frame_u8(self, scene, max_depth, seed, accumulate=False, denoise=False):
         """update()'s frame: 1 spp, only the u8 image copied back, by DMA into page-locked
         memory that `pixels` views (overwritten by the next frame, as tracer.rs's
         model.pixels is). The view keeps the page-locked block alive, so an array returned
         here stays valid memory after the model is closed or collected; copy it to keep a
         frame past the next update(). accumulate: the frame joins the context's accumulation
         (FR_FLAG_ACCUMULATE) and the image is the mean of every frame in it; "error": the
-        accumulation also carries the error estimate (model.ctx.accum_error)."""
+        accumulation also carries the error estimate (model.ctx.accum_error). denoise (with
+        accumulate "error" or "adaptive"): from the second frame of an accumulation on the image
+        is the accumulation's denoised u8 (RenderContext.denoise at the defaults); on its first
+        frame, which has no variance yet, the plain u8."""
+        if denoise and accumulate not in ("error", "adaptive"):
+            raise ValueError('denoise=True needs accumulate="error" or "adaptive": the filter is steered by the '
+                             "accumulation's variance")
         ctx = self.context()
         ctx.render(scene, self.scene.camera, make_params(self.width, self.height, 1, max_depth, seed,
                                                          accumulate=accumulate))
         self.last_stats = ctx.sync()
         if self._pinned is None:
             self._pinned = PinnedFrame(self.width, self.height)
-        ctx.download_into(u8=self._pinned.u8)
+        if denoise and ctx.accum_info()[0] >= 2:
+            ctx.denoise()
+            ctx.download_denoised_into(self._pinned.u8)
+        else:
+            ctx.download_into(u8=self._pinned.u8)
         self.pixels = self._pinned.u8.reshape(-1)
         return self.pixels
 
@@ -914,19 +963,24 @@ def create_model(width, height, scene=None):
     return TraceModel(scene, width, height)
 
 
-def update(model, keys, delta_time, max_depth=MAX_DEPTH, accumulate=False):
+def update(model, keys, delta_time, max_depth=MAX_DEPTH, accumulate=False, denoise=False):
     """tracer.rs:30-55: key bitmask 00EQADWS -> camera.orbit(delta), then one 1-spp frame
     into model.pixels. Each frame draws from its own RNG key. accumulate: while no key is
     pressed the frames add up on the model's context and model.pixels converges (the mean of
     every frame since the camera last moved); a key press moves the camera, which starts anew.
     accumulate="error": the same picture, and model.ctx.accum_error(threshold) tells how far the
-    accumulation has converged (FR_FLAG_ACCUM_ERROR)."""
+    accumulation has converged (FR_FLAG_ACCUM_ERROR). denoise=True (with accumulate="error" or
+    "adaptive", ValueError otherwise): model.pixels is the accumulation filtered by its own
+    per-pixel variance (RenderContext.denoise) from its second frame on, the plain picture on
+    its first frame and right after a key press restarts it."""
+    if denoise and accumulate not in ("error", "adaptive"):
+        raise ValueError('denoise=True needs accumulate="error" or "adaptive"')
     d = (C.c_float * 3)()
     check(lib().fr_update_delta(int(keys) & 0xFF, float(delta_time), d))
     camera_orbit(model.scene.camera, list(d))
     seed = model.seed ^ (0x9E3779B97F4A7C15 * (model.frame + 1) & 0xFFFFFFFFFFFFFFFF)
     model.frame += 1
-    return model.frame_u8(model.scene, max_depth, seed, accumulate=accumulate)
+    return model.frame_u8(model.scene, max_depth, seed, accumulate=accumulate, denoise=denoise)
 
 
 def write_png(path, rgb8):

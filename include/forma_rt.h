@@ -61,7 +61,8 @@ extern "C" {
                                fr_mctx_accum_reset / _info; FR_FLAG_ACCUM_ERROR,
                                fr_ctx_accum_error, fr_ctx_download_error, fr_mctx_accum_error;
                                FR_FLAG_ADAPTIVE, fr_adapt_info, fr_ctx_adapt, fr_ctx_download_counts,
-                               fr_mctx_adapt) */
+                               fr_mctx_adapt; fr_ctx_denoise, fr_ctx_download_denoised,
+                               fr_ctx_denoised_buffers) */
 
 /* error codes */
 #define FR_OK 0
@@ -369,6 +370,42 @@ int fr_ctx_adapt(fr_ctx* ctx, float threshold, uint32_t min_samples, fr_adapt_in
    K_t; the uniform n and K while it is not tiled): W x H uint32 each, either may be NULL; this
    shard's rows only. Waits for the enqueued resolves. FR_EARG without a live accumulation. */
 int fr_ctx_download_counts(fr_ctx* ctx, uint32_t* samples, uint32_t* frames);
+
+/* Variance-guided denoise of the live accumulation: an a-trous wavelet filter (SVGF's spatial
+   part) of the mean A / n, steered by the per-pixel variance of the mean that A, Q and the counts
+   give (each pixel's tile's n_t and K_t on a tiled accumulation). Prep: per channel m = A / n and
+   v as fr_ctx_accum_error's, C = (m_r, m_g, m_b), var = ((v_r + v_g) + v_b) / n; a pixel is valid
+   iff |m_c| <= FR_DN_MEAN_MAX in every channel and var <= FR_DN_VAR_MAX (a NaN or infinite pixel
+   is not). Level i = 0 .. levels-1 with step s = 1 << i: an invalid pixel keeps its bits; a valid
+   pixel p gets g = the (1 2 1) x (1 2 1) weighted mean of var over its valid 3x3 neighbours,
+   sden = k g + FR_DN_EPS, and over the 5x5 taps q = p + s (dx, dy) that are inside the image and
+   valid, dy outer and dx inner, w = (h[dy] h[dx]) sden / (sden + |C_q - C_p|^2) with
+   h = (1/16, 1/4, 3/8, 1/4, 1/16): C' = sum(w C_q) / sum(w), var' = sum(w^2 var_q) / sum(w)^2.
+   Every operation rounds once in f32 in a fixed order (fo-rma_amd/csrc/denoise.h), so the
+   result is the same bits every time. rgb8 = to_u8 of the filtered mean, as a frame's.
+   The variance that comes out is what the filter steered by, not an error estimate of the
+   filtered picture: the filter trades variance for bias, and on reference frames the map read
+   23 to 46 times under the real squared error.
+   Out of scope: shards. The 8-row strips of different shards live on different devices and a tap
+   reaches up to 2 * 2^(levels-1) rows away; the data path has no exchange step, so only a whole
+   image (shard_count 1) is filtered and there is no fr_mctx_denoise. */
+#define FR_DN_EPS 9.5367431640625e-07f /* 2^-20 */
+#define FR_DN_MEAN_MAX 1099511627776.0f /* 2^40 */
+#define FR_DN_VAR_MAX 1208925819614629174706176.0f /* 2^80 */
+#define FR_DN_LEVELS_DEFAULT 4u
+#define FR_DN_K_DEFAULT 4.0f
+/* Enqueue the filter on the live accumulation; returns at once. levels 1..6, k finite in (0, 1024].
+   It runs behind the resolve of every frame enqueued so far and reads A, Q and the counts only:
+   the outputs of the frames, the pending render and its stats are untouched, and the result
+   describes the accumulation as of the call (later frames do not update it).
+   FR_EARG: no live accumulation, no Q, fewer than two frames (the conditions of fr_ctx_accum_error),
+   shard_count != 1, levels or k out of range. */
+int fr_ctx_denoise(fr_ctx* ctx, uint32_t levels, float k);
+/* Waits for the last fr_ctx_denoise; any pointer may be NULL. FR_EARG if none was enqueued since
+   the buffers were (re)allocated. mean_rgb W*H*3 f32, rgb8 W*H*3 u8, var W*H f32. */
+int fr_ctx_download_denoised(fr_ctx* ctx, float* mean_rgb, uint8_t* rgb8, float* var);
+/* Device pointers of the denoised mean and u8 (for fr_rgb_to_rgba_device / fr_post_process_device). */
+int fr_ctx_denoised_buffers(fr_ctx* ctx, float** d_mean_rgb, uint8_t** d_rgb8);
 
 /* ---- persistent multi-device context (tracer.rs:83-134 render_mt, one device per shard) ----
    Entry i of `devices` renders row shard i of n of every frame on its own fr_ctx (device
