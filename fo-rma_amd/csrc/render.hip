@@ -29,6 +29,7 @@
 
 #include "accum_error.h"
 #include "denoise.h"
+#include "gbuffer.h"
 #include "hipchk.h"
 #include "jit.h"
 #include "pack.h"
@@ -205,6 +206,17 @@ struct fr_ctx {
   float* d_dn_var = nullptr;
   uint32_t dn_w = 0, dn_h = 0;
   bool dn_valid = false;
+  // fr_ctx_gbuffer: the view's feature buffers, W*H float4 each, allocated on
+  // first use and kept while the image size is unchanged, and their key: the scene upload, the
+  // camera's 104 bytes and the size they were enqueued for. gb_valid: a pass was enqueued since
+  // they were (re)allocated.
+  float4* d_gb0 = nullptr;
+  float4* d_gb1 = nullptr;
+  float4* d_gb_alb = nullptr;
+  uint32_t gb_w = 0, gb_h = 0;
+  uint64_t gb_uid = 0;
+  fr_camera gb_cam{};
+  bool gb_valid = false;
   // the last render was adaptive: the image pixels it traced (fr_stats), or none (empty list)
   bool last_adaptive = false, last_empty = false;
   uint64_t last_active_pixels = 0;
@@ -538,7 +550,8 @@ void fr_ctx_free(fr_ctx* c) {
                   static_cast<void*>(c->d_kt), static_cast<void*>(c->d_list), static_cast<void*>(c->d_tile_px),
                   static_cast<void*>(c->d_adapt_sum), static_cast<void*>(c->d_dn_ping),
                   static_cast<void*>(c->d_dn_pong), static_cast<void*>(c->d_dn_mean), static_cast<void*>(c->d_dn_u8),
-                  static_cast<void*>(c->d_dn_var)})
+                  static_cast<void*>(c->d_dn_var), static_cast<void*>(c->d_gb0), static_cast<void*>(c->d_gb1),
+                  static_cast<void*>(c->d_gb_alb)})
     if (d) (void)hipFree(d);
   for (hipEvent_t e : {c->ev0, c->ev1, c->ev_start, c->ev_copy})
     if (e) (void)hipEventDestroy(e);
@@ -1113,28 +1126,28 @@ int fr_ctx_adapt(fr_ctx* c, float threshold, uint32_t min_samples, fr_adapt_info
   return FR_OK;
 }
 
-// The filter on demand (DESIGN.md §4.5d). Like fr_ctx_accum_error's kernels, prep and the levels
-// go on the sum stream, behind the resolve of every frame enqueued so far and ahead of every
-// later one; unlike it nothing is waited for. A, Q, the counts, d_mean, d_u8, the pending
-// render and its stats are read or untouched: the results have buffers of their own.
-int fr_ctx_denoise(fr_ctx* c, uint32_t levels, float k) {
-  if (!c) return set_error(FR_EARG, "fr_ctx_denoise: null ctx");
+// What fr_ctx_denoise and fr_ctx_denoise_guided (`who`) refuse alike, before anything is enqueued.
+static int denoise_refusal(const fr_ctx* c, const char* who, uint32_t levels, float k) {
   if (levels < 1u || levels > kDnLevelsMax)
-    return set_error(FR_EARG, "fr_ctx_denoise: levels %u must be 1 to %u", levels, kDnLevelsMax);
+    return set_error(FR_EARG, "%s: levels %u must be 1 to %u", who, levels, kDnLevelsMax);
   if (!(k > 0.0f && k <= kDnKMax))
-    return set_error(FR_EARG, "fr_ctx_denoise: k %g must be finite, > 0 and <= %g", static_cast<double>(k),
+    return set_error(FR_EARG, "%s: k %g must be finite, > 0 and <= %g", who, static_cast<double>(k),
                      static_cast<double>(kDnKMax));
   const AccumState& a = c->accum;
-  if (!a.live) return set_error(FR_EARG, "fr_ctx_denoise: no live accumulation (no FR_FLAG_ACCUMULATE frame yet, or reset)");
+  if (!a.live) return set_error(FR_EARG, "%s: no live accumulation (no FR_FLAG_ACCUMULATE frame yet, or reset)", who);
   if (!a.has_q || !c->d_sq)
-    return set_error(FR_EARG, "fr_ctx_denoise: the live accumulation carries no Q: its frames lack FR_FLAG_ACCUM_ERROR");
+    return set_error(FR_EARG, "%s: the live accumulation carries no Q: its frames lack FR_FLAG_ACCUM_ERROR", who);
   if (a.frames < 2)
-    return set_error(FR_EARG, "fr_ctx_denoise: %u frame in the accumulation, the variance needs two", a.frames);
+    return set_error(FR_EARG, "%s: %u frame in the accumulation, the variance needs two", who, a.frames);
+  if (c->accum_kp.shard_count != 1)
+    return set_error(FR_EARG, "%s: shard_count %u: the filter's taps cross the strips of other shards, "
+                              "only a whole image (shard_count 1) is filtered", who, c->accum_kp.shard_count);
+  return FR_OK;
+}
+
+// The ping and pong buffers and the three outputs at the live accumulation's size.
+static int denoise_buffers(fr_ctx* c) {
   const KParams& kp = c->accum_kp;
-  if (kp.shard_count != 1)
-    return set_error(FR_EARG, "fr_ctx_denoise: shard_count %u: the filter's taps cross the strips of other shards, "
-                              "only a whole image (shard_count 1) is filtered", kp.shard_count);
-  SET_DEVICE(c->device);
   if (c->dn_w != kp.W || c->dn_h != kp.H || !c->d_dn_var) {
     // another size: the kernels and copies that use the old buffers are on the sum stream
     HIPCHK(hipStreamSynchronize(c->stream_sum));
@@ -1151,10 +1164,130 @@ int fr_ctx_denoise(fr_ctx* c, uint32_t levels, float k) {
     c->dn_w = kp.W;
     c->dn_h = kp.H;
   }
+  return FR_OK;
+}
+
+// The filter on demand (DESIGN.md §4.5d). Like fr_ctx_accum_error's kernels, prep and the levels
+// go on the sum stream, behind the resolve of every frame enqueued so far and ahead of every
+// later one; unlike it nothing is waited for. A, Q, the counts, d_mean, d_u8, the pending
+// render and its stats are read or untouched: the results have buffers of their own.
+int fr_ctx_denoise(fr_ctx* c, uint32_t levels, float k) {
+  if (!c) return set_error(FR_EARG, "fr_ctx_denoise: null ctx");
+  int rc;
+  if ((rc = denoise_refusal(c, "fr_ctx_denoise", levels, k))) return rc;
+  SET_DEVICE(c->device);
+  if ((rc = denoise_buffers(c))) return rc;
+  const AccumState& a = c->accum;
   const bool tiled = c->tiled.tiled;
-  HIPCHK(launch_denoise(c->stream_sum, kp, c->d_accum, c->d_sq, tiled ? c->d_nt : nullptr, tiled ? c->d_kt : nullptr,
-                        a.samples, a.frames, levels, k, c->d_dn_ping, c->d_dn_pong, c->d_dn_mean, c->d_dn_u8,
-                        c->d_dn_var));
+  HIPCHK(launch_denoise(c->stream_sum, c->accum_kp, c->d_accum, c->d_sq, tiled ? c->d_nt : nullptr,
+                        tiled ? c->d_kt : nullptr, a.samples, a.frames, levels, k, c->d_dn_ping, c->d_dn_pong,
+                        c->d_dn_mean, c->d_dn_u8, c->d_dn_var));
+  c->dn_valid = true;
+  return FR_OK;
+}
+
+// The view's feature buffers: one pass on the sum stream, behind whatever is
+// enqueued there; nothing is waited for. Frames, A, Q, d_mean, d_u8, the pending render and its
+// stats are untouched: the pass reads the scene's device copy and writes buffers of its own.
+int fr_ctx_gbuffer(fr_ctx* c, fr_scene* scene, const fr_camera* cam, uint32_t width, uint32_t height) {
+  if (!c || !scene || !cam) return set_error(FR_EARG, "fr_ctx_gbuffer: null argument");
+  if (!width || !height) return set_error(FR_EARG, "fr_ctx_gbuffer: width %u and height %u must be > 0", width, height);
+  if (static_cast<uint64_t>(width) * height > 0x7FFFFFFFull / 16u)
+    return set_error(FR_EARG, "fr_ctx_gbuffer: %u x %u pixels, at most 2^27 are supported", width, height);
+  SET_DEVICE(c->device);
+  const PlanEnv env = read_plan_env();
+  DeviceCopy* dc = nullptr;
+  int rc;
+  if ((rc = upload_scene(scene, c->device, env.bvh_force, &dc))) return rc;
+  if (c->gb_w != width || c->gb_h != height || !c->d_gb_alb) {
+    HIPCHK(hipStreamSynchronize(c->stream_sum));  // the kernels and copies that use the old buffers
+    c->gb_valid = false;
+    c->gb_w = c->gb_h = 0;
+    const size_t bytes = static_cast<size_t>(width) * height * sizeof(float4);
+    size_t caps[3] = {};  // (grow with no capacity: each buffer is replaced)
+    if ((rc = grow(c->d_gb0, caps[0], bytes))) return rc;
+    if ((rc = grow(c->d_gb1, caps[1], bytes))) return rc;
+    if ((rc = grow(c->d_gb_alb, caps[2], bytes))) return rc;
+    c->gb_w = width;
+    c->gb_h = height;
+  }
+  const PackedScene& ps = dc->ps;
+  const char* b = static_cast<const char*>(dc->blob);
+  GbScene gs;
+  gs.rec = reinterpret_cast<const float4*>(b + ps.off_rec);
+  gs.runs = reinterpret_cast<const uint4*>(b + ps.off_runs);
+  gs.cls = reinterpret_cast<const uint32_t*>(b + ps.off_cls);
+  gs.att = reinterpret_cast<const float4*>(b + ps.off_att);
+  gs.n_runs = ps.n_runs;
+  gs.n = ps.facts.n;
+  const GbCam gc{V3{cam->position[0], cam->position[1], cam->position[2]},
+                 V3{cam->lower_left[0], cam->lower_left[1], cam->lower_left[2]},
+                 V3{cam->horizontal[0], cam->horizontal[1], cam->horizontal[2]},
+                 V3{cam->vertical[0], cam->vertical[1], cam->vertical[2]}};
+  HIPCHK(launch_gbuffer(c->stream_sum, gs, gc, width, height, c->d_gb0, c->d_gb1, c->d_gb_alb));
+  c->gb_uid = dc->uid;
+  c->gb_cam = *cam;
+  c->gb_valid = true;
+  return FR_OK;
+}
+
+int fr_ctx_download_gbuffer(fr_ctx* c, uint32_t* prim, float* depth, float* normal, float* position, float* albedo) {
+  if (!c) return set_error(FR_EARG, "fr_ctx_download_gbuffer: null ctx");
+  if (!c->gb_valid) return set_error(FR_EARG, "fr_ctx_download_gbuffer: no G-buffer (fr_ctx_gbuffer first)");
+  SET_DEVICE(c->device);
+  const size_t px = static_cast<size_t>(c->gb_w) * c->gb_h;
+  // the device words are unpacked on the host: only the planes asked for are copied
+  const bool want0 = depth || normal, want1 = prim || position;
+  std::vector<float> g0(want0 ? 4 * px : 0), g1(want1 ? 4 * px : 0), al(albedo ? 4 * px : 0);
+  hipStream_t st = c->stream_sum;
+  if (want0) HIPCHK(hipMemcpyAsync(g0.data(), c->d_gb0, px * sizeof(float4), hipMemcpyDeviceToHost, st));
+  if (want1) HIPCHK(hipMemcpyAsync(g1.data(), c->d_gb1, px * sizeof(float4), hipMemcpyDeviceToHost, st));
+  if (albedo) HIPCHK(hipMemcpyAsync(al.data(), c->d_gb_alb, px * sizeof(float4), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  for (size_t i = 0; i < px; ++i) {
+    if (prim) memcpy(&prim[i], &g1[4 * i + 3], 4);
+    if (depth) depth[i] = g0[4 * i + 3];
+    if (normal) memcpy(&normal[3 * i], &g0[4 * i], 12);
+    if (position) memcpy(&position[3 * i], &g1[4 * i], 12);
+    if (albedo) memcpy(&albedo[3 * i], &al[4 * i], 12);
+  }
+  return FR_OK;
+}
+
+// The guided filter on demand: fr_ctx_denoise's place on the sum stream, behind
+// the G-buffer pass it reads (the same stream), into the same output buffers.
+int fr_ctx_denoise_guided(fr_ctx* c, uint32_t levels, float k, const fr_denoise_guide* g) {
+  if (!c) return set_error(FR_EARG, "fr_ctx_denoise_guided: null ctx");
+  static const char* who = "fr_ctx_denoise_guided";
+  int rc;
+  if ((rc = denoise_refusal(c, who, levels, k))) return rc;
+  const fr_denoise_guide dflt{kDnSigmaZDefault, kDnNormalPow2Default, 1u, 0u};
+  const fr_denoise_guide gd = g ? *g : dflt;
+  if (!(gd.sigma_z > 0.0f && gd.sigma_z <= kDnSigmaZMax))
+    return set_error(FR_EARG, "%s: sigma_z %g must be finite, > 0 and <= %g", who, static_cast<double>(gd.sigma_z),
+                     static_cast<double>(kDnSigmaZMax));
+  if (gd.normal_pow2 > kDnNormalPow2Max)
+    return set_error(FR_EARG, "%s: normal_pow2 %u must be 0 to %u", who, gd.normal_pow2, kDnNormalPow2Max);
+  if (gd.demodulate > 1u) return set_error(FR_EARG, "%s: demodulate %u must be 0 or 1", who, gd.demodulate);
+  if (gd.pad != 0u) return set_error(FR_EARG, "%s: pad %u must be 0", who, gd.pad);
+  if (!c->gb_valid) return set_error(FR_EARG, "%s: no G-buffer (fr_ctx_gbuffer first)", who);
+  const AccumState& a = c->accum;
+  const KParams& kp = c->accum_kp;
+  if (c->gb_uid != a.key.scene_uid)
+    return set_error(FR_EARG, "%s: the G-buffer is of another scene upload than the live accumulation", who);
+  if (memcmp(&c->gb_cam, &a.key.cam, sizeof(fr_camera)) != 0)
+    return set_error(FR_EARG, "%s: the G-buffer is of another camera than the live accumulation", who);
+  if (c->gb_w != kp.W)
+    return set_error(FR_EARG, "%s: the G-buffer's width %u differs from the live accumulation's %u", who, c->gb_w, kp.W);
+  if (c->gb_h != kp.H)
+    return set_error(FR_EARG, "%s: the G-buffer's height %u differs from the live accumulation's %u", who, c->gb_h, kp.H);
+  SET_DEVICE(c->device);
+  if ((rc = denoise_buffers(c))) return rc;
+  const bool tiled = c->tiled.tiled;
+  HIPCHK(launch_denoise_guided(c->stream_sum, kp, c->d_accum, c->d_sq, tiled ? c->d_nt : nullptr,
+                               tiled ? c->d_kt : nullptr, a.samples, a.frames, levels, k,
+                               DnGuide{gd.sigma_z, gd.normal_pow2, gd.demodulate}, c->d_gb0, c->d_gb1, c->d_gb_alb,
+                               c->d_dn_ping, c->d_dn_pong, c->d_dn_mean, c->d_dn_u8, c->d_dn_var));
   c->dn_valid = true;
   return FR_OK;
 }

@@ -45,6 +45,11 @@ FR_ERR_FLOOR = 2.0 ** -7  # the relative error's smallest denominator (forma_rt.
 # fr_ctx_denoise (forma_rt.h): the defaults, the edge-stopping floor and the validity caps
 FR_DN_LEVELS_DEFAULT, FR_DN_K_DEFAULT = 4, 4.0
 FR_DN_EPS, FR_DN_MEAN_MAX, FR_DN_VAR_MAX = 2.0 ** -20, 2.0 ** 40, 2.0 ** 80
+# fr_ctx_gbuffer / fr_ctx_denoise_guided (forma_rt.h): the miss id, the feature and albedo caps
+# and the guide's defaults
+FR_GBUFFER_MISS = 0xFFFFFFFF
+FR_DN_FEAT_MAX, FR_DN_NORMAL_MAX, FR_DN_ALB_MIN, FR_DN_ALB_MAX = 2.0 ** 40, 2.0 ** 10, 2.0 ** -6, 2.0 ** 6
+FR_DN_SIGMA_Z_DEFAULT, FR_DN_NORMAL_POW2_DEFAULT = 2.0 ** -5, 4
 FR_JIT_OFF, FR_JIT_USED, FR_JIT_PENDING, FR_JIT_FAILED, FR_JIT_MISS = 0, 1, 2, 3, 4  # fr_ctx_jit_state
 MAX_DEPTH = 50  # tracer.rs:10
 DEFAULT_SEED = 0x5EED
@@ -105,6 +110,10 @@ class FrAdaptInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
 
 
+class FrDenoiseGuide(C.Structure):
+    _fields_ = [("sigma_z", C.c_float), ("normal_pow2", C.c_uint32), ("demodulate", C.c_uint32), ("pad", C.c_uint32)]
+
+
 # Every symbol include/forma_rt.h declares (checked by tests/test_abi.py).
 EXPORTS = (
     "fr_last_error", "fr_abi_version", "fr_device_count",
@@ -123,6 +132,7 @@ EXPORTS = (
     "fr_ctx_accum_error", "fr_ctx_download_error", "fr_mctx_accum_error",
     "fr_ctx_adapt", "fr_ctx_download_counts", "fr_mctx_adapt",
     "fr_ctx_denoise", "fr_ctx_download_denoised", "fr_ctx_denoised_buffers",
+    "fr_ctx_gbuffer", "fr_ctx_download_gbuffer", "fr_ctx_denoise_guided",
 )
 
 _lib = None
@@ -232,6 +242,10 @@ def lib():
         L.fr_ctx_denoise.argtypes = [vp, C.c_uint32, C.c_float]
         L.fr_ctx_download_denoised.argtypes = [vp, f3, P(C.c_uint8), f3]
         L.fr_ctx_denoised_buffers.argtypes = [vp, P(vp), P(vp)]
+    if hasattr(L, "fr_ctx_gbuffer"):
+        L.fr_ctx_gbuffer.argtypes = [vp, vp, P(FrCamera), C.c_uint32, C.c_uint32]
+        L.fr_ctx_download_gbuffer.argtypes = [vp, P(C.c_uint32), f3, f3, f3, f3]
+        L.fr_ctx_denoise_guided.argtypes = [vp, C.c_uint32, C.c_float, P(FrDenoiseGuide)]
     _lib = L
     return L
 
@@ -638,13 +652,41 @@ class RenderContext:
                                            frames.ctypes.data_as(C.POINTER(C.c_uint32))))
         return samples, frames
 
-    def denoise(self, levels=FR_DN_LEVELS_DEFAULT, k=FR_DN_K_DEFAULT):
+    def denoise(self, levels=FR_DN_LEVELS_DEFAULT, k=FR_DN_K_DEFAULT, guided=False, sigma_z=FR_DN_SIGMA_Z_DEFAULT,
+                normal_pow2=FR_DN_NORMAL_POW2_DEFAULT, demodulate=True):
         """Enqueues the variance-guided filter of the live accumulation (fr_ctx_denoise: frames
         of make_params(accumulate="error") or "adaptive", two or more, shard_count 1) and
         returns at once: `levels` a-trous levels (1 to 6, steps 1, 2, 4, ...) with edge-stopping
         scale k (0 < k <= 1024). The result describes the accumulation as of the call;
-        download_denoised() waits for it. The frames' own outputs are untouched."""
-        check(lib().fr_ctx_denoise(self._h, int(levels), float(k)))
+        download_denoised() waits for it. The frames' own outputs are untouched.
+        guided: the feature-guided filter instead (fr_ctx_denoise_guided), steered also by the
+        G-buffer of the same scene, camera and size (gbuffer() first): sigma_z in (0, 1024]
+        scales the plane-distance weight by the depth, the normal weight is the clamped dot
+        product to the power 2^normal_pow2 (0 to 8), demodulate filters the colour divided by
+        the first hit's albedo. The three are ignored without guided."""
+        if not guided:
+            check(lib().fr_ctx_denoise(self._h, int(levels), float(k)))
+            return
+        g = FrDenoiseGuide(float(sigma_z), int(normal_pow2), int(demodulate), 0)
+        check(lib().fr_ctx_denoise_guided(self._h, int(levels), float(k), C.byref(g)))
+
+    def gbuffer(self, scene, cam, width, height):
+        """Enqueues the first-hit feature pass of the view (fr_ctx_gbuffer) and returns at once:
+        per pixel the pinhole primary ray's closest primitive, its root, normal, point and
+        albedo. Renders, the accumulation and their outputs are untouched. It tests every
+        primitive for every pixel: once per view, not per frame."""
+        check(lib().fr_ctx_gbuffer(self._h, scene._h, C.byref(cam), int(width), int(height)))
+
+    def download_gbuffer(self, width, height):
+        """The last gbuffer() as a dict: "prim" [H, W] uint32 (FR_GBUFFER_MISS for a miss),
+        "depth" [H, W] f32, "normal", "position" and "albedo" [H, W, 3] f32. Waits for it."""
+        out = {"prim": np.zeros((height, width), dtype=np.uint32), "depth": np.zeros((height, width), dtype=np.float32)}
+        for name in ("normal", "position", "albedo"):
+            out[name] = np.zeros((height, width, 3), dtype=np.float32)
+        fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))  # noqa: E731
+        check(lib().fr_ctx_download_gbuffer(self._h, out["prim"].ctypes.data_as(C.POINTER(C.c_uint32)), fp(out["depth"]),
+                                            fp(out["normal"]), fp(out["position"]), fp(out["albedo"])))
+        return out
 
     def download_denoised(self, width, height, want_var=False):
         """(mean [H, W, 3] f32, u8 [H, W, 3]) of the last denoise(), with want_var also the
@@ -925,18 +967,24 @@ class TraceModel:
         accumulation also carries the error estimate (model.ctx.accum_error). denoise (with
         accumulate "error" or "adaptive"): from the second frame of an accumulation on the image
         is the accumulation's denoised u8 (RenderContext.denoise at the defaults); on its first
-        frame, which has no variance yet, the plain u8."""
+        frame, which has no variance yet, the plain u8. denoise="guided": the feature-guided
+        filter at its defaults; the view's G-buffer is enqueued when an accumulation starts."""
+        if denoise not in (False, True, "guided"):
+            raise ValueError(f'denoise={denoise!r}: False, True or "guided"')
         if denoise and accumulate not in ("error", "adaptive"):
-            raise ValueError('denoise=True needs accumulate="error" or "adaptive": the filter is steered by the '
-                             "accumulation's variance")
+            raise ValueError(f'denoise={denoise!r} needs accumulate="error" or "adaptive": the filter is steered by '
+                             "the accumulation's variance")
         ctx = self.context()
         ctx.render(scene, self.scene.camera, make_params(self.width, self.height, 1, max_depth, seed,
                                                          accumulate=accumulate))
         self.last_stats = ctx.sync()
         if self._pinned is None:
             self._pinned = PinnedFrame(self.width, self.height)
+        guided = denoise == "guided"
+        if guided and ctx.accum_info()[0] == 1:  # a new accumulation: a new view
+            ctx.gbuffer(scene, self.scene.camera, self.width, self.height)
         if denoise and ctx.accum_info()[0] >= 2:
-            ctx.denoise()
+            ctx.denoise(guided=guided)
             ctx.download_denoised_into(self._pinned.u8)
         else:
             ctx.download_into(u8=self._pinned.u8)
@@ -972,9 +1020,13 @@ def update(model, keys, delta_time, max_depth=MAX_DEPTH, accumulate=False, denoi
     accumulation has converged (FR_FLAG_ACCUM_ERROR). denoise=True (with accumulate="error" or
     "adaptive", ValueError otherwise): model.pixels is the accumulation filtered by its own
     per-pixel variance (RenderContext.denoise) from its second frame on, the plain picture on
-    its first frame and right after a key press restarts it."""
+    its first frame and right after a key press restarts it. denoise="guided": the same with the
+    feature-guided filter (RenderContext.denoise(guided=True)), whose G-buffer is enqueued on the
+    first frame of each accumulation."""
+    if denoise not in (False, True, "guided"):
+        raise ValueError(f'denoise={denoise!r}: False, True or "guided"')
     if denoise and accumulate not in ("error", "adaptive"):
-        raise ValueError('denoise=True needs accumulate="error" or "adaptive"')
+        raise ValueError(f'denoise={denoise!r} needs accumulate="error" or "adaptive"')
     d = (C.c_float * 3)()
     check(lib().fr_update_delta(int(keys) & 0xFF, float(delta_time), d))
     camera_orbit(model.scene.camera, list(d))

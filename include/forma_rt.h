@@ -62,7 +62,8 @@ extern "C" {
                                fr_ctx_accum_error, fr_ctx_download_error, fr_mctx_accum_error;
                                FR_FLAG_ADAPTIVE, fr_adapt_info, fr_ctx_adapt, fr_ctx_download_counts,
                                fr_mctx_adapt; fr_ctx_denoise, fr_ctx_download_denoised,
-                               fr_ctx_denoised_buffers) */
+                               fr_ctx_denoised_buffers; fr_ctx_gbuffer, fr_ctx_download_gbuffer,
+                               fr_denoise_guide, fr_ctx_denoise_guided) */
 
 /* error codes */
 #define FR_OK 0
@@ -406,6 +407,70 @@ int fr_ctx_denoise(fr_ctx* ctx, uint32_t levels, float k);
 int fr_ctx_download_denoised(fr_ctx* ctx, float* mean_rgb, uint8_t* rgb8, float* var);
 /* Device pointers of the denoised mean and u8 (for fr_rgb_to_rgba_device / fr_post_process_device). */
 int fr_ctx_denoised_buffers(fr_ctx* ctx, float** d_mean_rgb, uint8_t** d_rgb8);
+
+/* First-hit feature buffers of a view (AOV output, and what fr_ctx_denoise_guided steers by): per
+   pixel (x, y) of the W x H image the pinhole primary ray
+     u = ((float)x + 0.5) / (float)W, v = ((float)(H - y) + 0.5) / (float)H,
+     o = position, d = ((lower_left + u horizontal) + v vertical) - position
+   (get_ray with the jitter fixed at 0.5; lens_radius is ignored) through the scene's closest-hit
+   loop: list order, t_min = 0.001, t_max = the closest root so far, strict comparisons, every
+   operation rounded once in f32 (fo-rma_amd/csrc/gbuffer.h). prim = the winner's list index or
+   FR_GBUFFER_MISS; depth = the winner's own accepted root t (not the shared hit record's last
+   written t, which a later plane can leave stale); normal = the winner's normal at that root;
+   position = o + t d; albedo = the primitive's attenuation (its colour, or 1 for the light
+   material). A miss has depth 0, normal and position 0 and albedo 1.
+   fr_ctx_gbuffer uploads or reuses the scene's device copy, enqueues one pass behind the
+   context's enqueued resolves and returns at once; the buffers are keyed by that upload, the
+   camera's 104 bytes, W and H, allocated on first use and kept while the size is unchanged.
+   Frames, the accumulation, the outputs of the frames, the pending render and its stats are
+   untouched. The pass tests every primitive of the list for every pixel (no BVH): it is meant
+   to run once per view, not once per frame. FR_EARG for a width or height of 0 and for more than
+   2^27 pixels. */
+#define FR_GBUFFER_MISS 0xFFFFFFFFu
+int fr_ctx_gbuffer(fr_ctx* ctx, fr_scene* scene, const fr_camera* cam, uint32_t width, uint32_t height);
+/* Waits for the last fr_ctx_gbuffer; any pointer may be NULL. prim and depth W*H, normal,
+   position and albedo W*H*3, row-major. FR_EARG if no G-buffer was enqueued since the buffers were
+   (re)allocated. */
+int fr_ctx_download_gbuffer(fr_ctx* ctx, uint32_t* prim, float* depth, float* normal, float* position,
+                            float* albedo);
+
+/* Feature-guided denoise of the live accumulation: fr_ctx_denoise's a-trous filter with every
+   non-centre tap's weight extended by the G-buffer of the same view.
+   Prep: fr_ctx_denoise's m, var and validity; a hit pixel is also invalid unless depth <=
+   FR_DN_FEAT_MAX, |position_c| <= FR_DN_FEAT_MAX and |normal_c| <= FR_DN_NORMAL_MAX (comparisons
+   with NaN are false). With demodulate: a_c = albedo_c if FR_DN_ALB_MIN <= albedo_c <=
+   FR_DN_ALB_MAX, else 1; C_c = m_c / a_c and var = ((v_r / (a_r a_r) + v_g / (a_g a_g)) +
+   v_b / (a_b a_b)) / n. Without: a = 1 and the pixel is fr_ctx_denoise's.
+   Level: fr_ctx_denoise's loops, order and variance prefilter. A tap is also skipped unless it
+   and the centre are both hits or both misses. Between two hits
+     c = (N_p.x N_q.x + N_p.y N_q.y) + N_p.z N_q.z, c = c > 0 ? c : 0, wn = c squared normal_pow2 times,
+     e = dot(N_p, P_q - P_p) in the same association, z = sigma_z t_p, zden = z z + FR_DN_EPS,
+     wz = zden / (zden + e e),   w = (((h h) wc) wn) wz;
+   between two misses, and for the centre tap by definition, wn = wz = 1.
+   Last level: mean_c = C'_c a_c for every pixel, rgb8 = to_u8 of that mean, and var is the
+   variance the filter steered by in the demodulated space (of C, not of the mean); like
+   fr_ctx_denoise's it is no error estimate of the filtered picture.
+   The results land in fr_ctx_denoise's output buffers: fr_ctx_download_denoised and
+   fr_ctx_denoised_buffers serve the last denoise of either kind. Shards are out of scope as for
+   fr_ctx_denoise. */
+#define FR_DN_FEAT_MAX 1099511627776.0f /* 2^40 */
+#define FR_DN_NORMAL_MAX 1024.0f /* 2^10 */
+#define FR_DN_ALB_MIN 0.015625f /* 2^-6 */
+#define FR_DN_ALB_MAX 64.0f /* 2^6 */
+#define FR_DN_SIGMA_Z_DEFAULT 0.03125f /* 2^-5 */
+#define FR_DN_NORMAL_POW2_DEFAULT 4u
+typedef struct fr_denoise_guide {
+  float sigma_z;        /* finite, in (0, 1024] */
+  uint32_t normal_pow2; /* 0..8: the normal weight is max(dot, 0)^(2^normal_pow2) */
+  uint32_t demodulate;  /* 0 or 1 */
+  uint32_t pad;         /* 0 */
+} fr_denoise_guide;     /* 16 bytes */
+/* Enqueue the guided filter; returns at once. guide NULL: FR_DN_SIGMA_Z_DEFAULT,
+   FR_DN_NORMAL_POW2_DEFAULT, demodulate 1. FR_EARG, with nothing enqueued: everything
+   fr_ctx_denoise refuses, a guide field out of range, no G-buffer, and a G-buffer whose scene
+   upload, camera, width or height differs from the live accumulation's (fr_last_error says
+   which). */
+int fr_ctx_denoise_guided(fr_ctx* ctx, uint32_t levels, float k, const fr_denoise_guide* guide);
 
 /* ---- persistent multi-device context (tracer.rs:83-134 render_mt, one device per shard) ----
    Entry i of `devices` renders row shard i of n of every frame on its own fr_ctx (device
