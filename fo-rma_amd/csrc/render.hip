@@ -143,6 +143,7 @@ struct fr_ctx {
   bool copy_pending = false;
   int passes = 0;
   int occupancy = 0;  // trace-kernel workgroups per CU of the last launch (occupancy API)
+  bool cam_axial = false;  // the last prepared or rendered frame's camera rays take cam_ray_axial
   float* d_mean = nullptr;
   uint8_t* d_u8 = nullptr;
   // [0..3] counters, [4..30] and [32..63] diagnostics (FR_SECCNT, FR_PROF, FR_DIAG builds);
@@ -459,7 +460,31 @@ static KScene kscene(const DeviceCopy* dc, const FramePlan& fp) {
   return ks;
 }
 
-static KCam kcam(const fr_camera* cam) {
+// Whether Camera::get_ray's short form (trace_kernel.h cam_ray_axial) gives this camera's rays
+// bit for bit: the argument, term by term, is DESIGN.md §4.2. Every condition is needed by
+// one dropped operation; a camera that fails any takes cam_ray, which is untouched.
+static bool is_zero(float x) { return x == 0.0f; }                    // +0 or -0
+static bool is_neg_zero(float x) { return x == 0.0f && std::signbit(x); }
+static bool cam_axial(const KCam& k) {
+  const float all[] = {k.px, k.py, k.pz, k.lx, k.ly, k.lz, k.hx, k.hy, k.hz, k.vx,
+                       k.vy, k.vz, k.ux, k.uy, k.uz, k.bx, k.by, k.bz, k.lens, k.dz};
+  for (float x : all)
+    if (!std::isfinite(x)) return false;
+  // the lens offset's products use lens_s (exact) and never underflow to a zero that the
+  // lens draw did not put there
+  if (!(k.lens_pre & kCamLensPre) || !(k.lens > 0.0f)) return false;
+  if (!(k.lens_s * fabsf(k.ux) >= 0x1p-100f) || !(k.lens_s * fabsf(k.by) >= 0x1p-100f)) return false;
+  // the eight components whose products are dropped
+  if (!(is_zero(k.uy) && is_zero(k.uz) && is_zero(k.bx) && is_zero(k.bz) && is_zero(k.hy) && is_zero(k.hz) &&
+        is_zero(k.vx) && is_zero(k.vz)))
+    return false;
+  // a dropped +-0 addend changes only a -0 partner: no partner may be -0
+  if (is_zero(k.lx) || is_zero(k.ly) || is_zero(k.lz)) return false;
+  if (is_neg_zero(k.px) || is_neg_zero(k.py) || is_neg_zero(k.pz)) return false;
+  return true;
+}
+
+static KCam kcam(const fr_camera* cam, bool allow_axial = true) {
   KCam kc;
   kc.px = cam->position[0], kc.py = cam->position[1], kc.pz = cam->position[2];
   kc.lx = cam->lower_left[0], kc.ly = cam->lower_left[1], kc.lz = cam->lower_left[2];
@@ -469,8 +494,20 @@ static KCam kcam(const fr_camera* cam) {
   kc.bx = cam->v[0], kc.by = cam->v[1], kc.bz = cam->v[2];
   kc.lens = cam->lens_radius;
   kc.lens_s = ldexpf(kc.lens, -23);
-  kc.lens_pre = std::isfinite(kc.lens) && ldexpf(kc.lens_s, 23) == kc.lens ? 1u : 0u;
+  kc.lens_pre = std::isfinite(kc.lens) && ldexpf(kc.lens_s, 23) == kc.lens ? kCamLensPre : 0u;
+  kc.dz = kc.lz - kc.pz;
+  if (allow_axial && cam_axial(kc)) kc.lens_pre |= kCamAxial;
   return kc;
+}
+
+// A/B and tests: FR_CAM_GENERAL=1 sends every camera through cam_ray (read per frame)
+static bool cam_general_forced() {
+  const char* e = getenv("FR_CAM_GENERAL");
+  return e && *e && strcmp(e, "0") != 0;
+}
+
+namespace fr {
+KCam kcam_for_selftest(const fr_camera* cam) { return kcam(cam); }  // selftest.hip
 }
 
 extern "C" {
@@ -749,10 +786,12 @@ static int render_impl(fr_ctx* c, fr_scene* scene, const fr_camera* cam, const f
   kw.counters = c->d_cnt + kCntWords * fs;
   SceneKernel sk;
   if ((rc = find_scene_kernel(c, dc, fp, &sk))) return rc;
+  const KCam kc = kcam(cam, !cam_general_forced());
+  c->cam_axial = (kc.lens_pre & kCamAxial) != 0;
   if (dry) {
     c->jit_used = sk.fn != nullptr;
   } else {
-    if ((rc = enqueue_frame(c, dc, fp, KArgs{kscene(dc, fp), kcam(cam), fp.kp, kw}, sk, fs,
+    if ((rc = enqueue_frame(c, dc, fp, KArgs{kscene(dc, fp), kc, fp.kp, kw}, sk, fs,
                             accumulate ? &acc : nullptr)))
       return rc;
     if (accumulate) {
@@ -998,6 +1037,17 @@ int fr_ctx_jit_state(fr_ctx* c, int* state) {
 }
 
 int fr_jit_wait(void) { return jit_wait_all(); }
+
+int fr_camera_axial(const fr_camera* cam) {
+  if (!cam) return set_error(FR_EARG, "fr_camera_axial: null camera");
+  return (kcam(cam).lens_pre & kCamAxial) ? 1 : 0;
+}
+
+int fr_ctx_camera_path(fr_ctx* c, int* axial) {
+  if (!c || !axial) return set_error(FR_EARG, "fr_ctx_camera_path: null argument");
+  *axial = c->cam_axial ? 1 : 0;
+  return FR_OK;
+}
 
 int fr_ctx_accum_reset(fr_ctx* c) {
   if (!c) return set_error(FR_EARG, "fr_ctx_accum_reset: null ctx");

@@ -425,12 +425,53 @@ FR_HD float slab_d(float c, float inv, float oinv) {
 #endif
   return fmaf(c, inv, -oinv);
 }
+// slab3_fused, per axis: the two slab distances t0, t1 and their near / far order.
+//
+// Symmetric pair. When lo and hi are compile-time constants (the scene kernel's records) with
+// lo = -hi and 0 < hi <= kSlabSymMax, the distances are formed already sorted:
+//   nr = fma(-hi, |inv|, -oinv),  fr = fma(hi, |inv|, -oinv)      (|inv| is a source modifier)
+// and the v_min_f32 / v_max_f32 of the pair is not needed. {nr, fr} are the bits of {t0, t1}:
+// for inv >= 0 they are the same operands, for inv < 0 the products (-hi)(-inv) and hi (-inv)
+// are those of hi inv and lo inv exactly, sign included, so each fma has the operands of the
+// other plane's. And nr <= fr whenever they are numbers, an fma being monotonic in its product.
+//   - NaN: hi |inv| <= 2^27 2^100 is finite (kSlabSymMax and the clamp; an unbounded hi could
+//     give fr = inf - inf beside a finite nr, which minNum / maxNum would both replace by nr), so
+//     a distance is NaN only through oinv, which both share: both are NaN, as without the shortcut, and the
+//     NaN-ignoring tn / tf see the same thing.
+//   - inv = +-0 (d = +-inf): both products are zeros and both distances are -oinv, or zeros when
+//     oinv is one; equal values have no order to get wrong.
+//   - inv = +-2^100 (the clamp of a tiny or zero d): an ordinary finite inv, covered above.
+//   - a zero distance (or two) may come out with the other sign than minNum / maxNum would pick:
+//     §3.3 shows neither the root selection (t > t_min > 0) nor the face test (t == a
+//     distance, +0 == -0) can see it.
+// t0 / t1 hold nr / fr, the same two values: slab_normal's min / max of them are unchanged.
+// Every other axis, every host build and every kernel whose records are loaded (is-constant
+// is false there) takes the plain expressions.
+constexpr float kSlabSymMax = 0x1p27f;
+FR_HD bool slab_sym(float lo, float hi) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_constant_p(lo) && __builtin_constant_p(hi) && lo == -hi && hi > 0.0f && hi <= kSlabSymMax;
+#else
+  (void)lo, (void)hi;
+  return false;
+#endif
+}
+// the distance of the plane at c (lo or hi) of an axis, and the axis's near / far distance
+FR_HD float slab_pair_d(float lo, float hi, float c, float inv, float oinv) {
+  return slab_sym(lo, hi) ? fmaf(c, __builtin_fabsf(inv), -oinv) : slab_d(c, inv, oinv);
+}
+FR_HD float slab_near(float lo, float hi, float t0, float t1) { return slab_sym(lo, hi) ? t0 : fmin_num(t0, t1); }
+FR_HD float slab_far(float lo, float hi, float t0, float t1) { return slab_sym(lo, hi) ? t1 : fmax_num(t0, t1); }
 FR_HD Slab slab3_fused(V3 lo, V3 hi, V3 oinv, V3 inv) {
   Slab s;
-  s.t0 = V3{slab_d(lo.x, inv.x, oinv.x), slab_d(lo.y, inv.y, oinv.y), slab_d(lo.z, inv.z, oinv.z)};
-  s.t1 = V3{slab_d(hi.x, inv.x, oinv.x), slab_d(hi.y, inv.y, oinv.y), slab_d(hi.z, inv.z, oinv.z)};
-  s.tn = fmax3_num(fmin_num(s.t0.x, s.t1.x), fmin_num(s.t0.y, s.t1.y), fmin_num(s.t0.z, s.t1.z));
-  s.tf = fmin3_num(fmax_num(s.t0.x, s.t1.x), fmax_num(s.t0.y, s.t1.y), fmax_num(s.t0.z, s.t1.z));
+  s.t0 = V3{slab_pair_d(lo.x, hi.x, lo.x, inv.x, oinv.x), slab_pair_d(lo.y, hi.y, lo.y, inv.y, oinv.y),
+            slab_pair_d(lo.z, hi.z, lo.z, inv.z, oinv.z)};
+  s.t1 = V3{slab_pair_d(lo.x, hi.x, hi.x, inv.x, oinv.x), slab_pair_d(lo.y, hi.y, hi.y, inv.y, oinv.y),
+            slab_pair_d(lo.z, hi.z, hi.z, inv.z, oinv.z)};
+  s.tn = fmax3_num(slab_near(lo.x, hi.x, s.t0.x, s.t1.x), slab_near(lo.y, hi.y, s.t0.y, s.t1.y),
+                   slab_near(lo.z, hi.z, s.t0.z, s.t1.z));
+  s.tf = fmin3_num(slab_far(lo.x, hi.x, s.t0.x, s.t1.x), slab_far(lo.y, hi.y, s.t0.y, s.t1.y),
+                   slab_far(lo.z, hi.z, s.t0.z, s.t1.z));
   return s;
 }
 

@@ -6,8 +6,22 @@
 
 #include "hipchk.h"
 #include "rt_core.h"
+#include "trace_kernel.h"
 
 namespace fr {
+
+KCam kcam_for_selftest(const fr_camera* cam);  // render.hip: the frame's own KCam of this camera
+
+// Camera::get_ray by both forms (trace_kernel.h cam_ray, cam_ray_axial) for tuple i
+__global__ void camray_kernel(KCam cm, const float* in, uint32_t n, uint32_t* out) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float kx = in[4 * i], ky = in[4 * i + 1], s = in[4 * i + 2], t = in[4 * i + 3];
+  const CamLens rd = cam_lens(cm, kx, ky);
+  const CamRay g = cam_ray(cm, rd, s, t), a = cam_ray_axial(cm, rd, s, t);
+  const float w[12] = {g.o.x, g.o.y, g.o.z, g.d.x, g.d.y, g.d.z, a.o.x, a.o.y, a.o.z, a.d.x, a.d.y, a.d.z};
+  for (int k = 0; k < 12; ++k) out[12 * i + k] = __float_as_uint(w[k]);
+}
 
 __global__ void ops_kernel(int op, const float* a, const float* b, uint32_t n, float* out) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -149,6 +163,24 @@ int fr_selftest_rng(int device, uint64_t seed, uint32_t pixel, uint32_t sample, 
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpy(out, d, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
   HIPCHK(hipFree(d));
+  return FR_OK;
+}
+
+int fr_selftest_camray(int device, const fr_camera* cam, const float* in, uint32_t n, uint32_t* out) {
+  if (!cam || !in || !out) return set_error(FR_EARG, "fr_selftest_camray: null argument");
+  const KCam kc = kcam_for_selftest(cam);
+  if (!(kc.lens_pre & kCamAxial)) return set_error(FR_EARG, "fr_selftest_camray: not an axial camera");
+  SET_DEVICE(device);
+  float* din = nullptr;
+  uint32_t* dout = nullptr;
+  HIPCHK(hipMalloc(&din, (n ? n : 1) * 4 * sizeof(float)));
+  HIPCHK(hipMalloc(&dout, (n ? n : 1) * 12 * sizeof(uint32_t)));
+  HIPCHK(hipMemcpy(din, in, n * 4 * sizeof(float), hipMemcpyHostToDevice));
+  if (n) hipLaunchKernelGGL(camray_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, kc, din, n, dout);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpy(out, dout, n * 12 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  HIPCHK(hipFree(din));
+  HIPCHK(hipFree(dout));
   return FR_OK;
 }
 

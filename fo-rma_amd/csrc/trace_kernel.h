@@ -97,9 +97,51 @@ struct KWork {
 struct KCam {
   float px, py, pz, lx, ly, lz, hx, hy, hz, vx, vy, vz, ux, uy, uz, bx, by, bz, lens;
   float lens_s;       // lens 2^-23
-  uint32_t lens_pre;  // lens_s is exact (no underflow): the lens sample uses it
+  // kCamLensPre: lens_s is exact (no underflow): the lens sample uses it
+  // kCamAxial:   the camera is of the axis-aligned class (cam_axial): cam_ray_axial's terms
+  uint32_t lens_pre;
+  float dz;           // RN(lz - pz), the axial ray's d.z (the same f32 subtraction, on the host)
 };
-static_assert(sizeof(KCam) == 21 * 4, "KCam is 21 words");
+static_assert(sizeof(KCam) == 22 * 4, "KCam is 22 words");
+constexpr uint32_t kCamLensPre = 1u, kCamAxial = 2u;
+
+// Camera::get_ray (camera.rs:62-72) for the lens point rd = lens (kx, ky) 2^-23 (cam_lens) and
+// the jittered (s, t).
+struct CamRay {
+  V3 o, d;
+};
+// lens * (k 2^-23) = (lens 2^-23) * k when lens 2^-23 is exact (kCamLensPre): the same
+// product, one rounding. kx, ky: the integers of the 2^23-scaled rejection test.
+struct CamLens {
+  float x, y;
+};
+__host__ __device__ __forceinline__ CamLens cam_lens(const KCam& cm, float kx, float ky) {
+  if (__builtin_expect((cm.lens_pre & kCamLensPre) != 0u, 1)) return CamLens{cm.lens_s * kx, cm.lens_s * ky};
+  return CamLens{cm.lens * (kx * kSignedUnitScale), cm.lens * (ky * kSignedUnitScale)};
+}
+__host__ __device__ __forceinline__ CamRay cam_ray(const KCam& cm, CamLens rd, float s, float t) {
+  const V3 cpos{cm.px, cm.py, cm.pz}, cllc{cm.lx, cm.ly, cm.lz}, chor{cm.hx, cm.hy, cm.hz};
+  const V3 cver{cm.vx, cm.vy, cm.vz}, cu{cm.ux, cm.uy, cm.uz}, cv{cm.bx, cm.by, cm.bz};
+  const V3 off = add(scl(rd.x, cu), scl(rd.y, cv));
+  return CamRay{add(cpos, off), sub(sub(add(add(cllc, scl(s, chor)), scl(t, cver)), cpos), off)};
+}
+// The same ray for a camera of the axial class (KCam::lens_pre & kCamAxial, decided by the
+// host's cam_axial): u = (ux, +-0, +-0), v = (+-0, vy, +-0), horizontal = (hx, +-0, +-0),
+// vertical = (+-0, vy', +-0). The products with those zeros and the additions of the zeros
+// they give are dropped: 16 operations for cam_ray's 32, the same bits (DESIGN.md §4.2
+// goes through them term by term; fr_selftest_camray compares the two on the device).
+__host__ __device__ __forceinline__ CamRay cam_ray_axial(const KCam& cm, CamLens rd, float s, float t) {
+  const float ox = rd.x * cm.ux, oy = rd.y * cm.by;
+  float oz = cm.pz, dz = cm.dz;
+#if defined(__HIP_DEVICE_COMPILE__)
+  // the two uniform values enter their lane registers here: the compiler otherwise moves the
+  // copies to the block where this form and cam_ray join, and cam_ray's side runs them too
+  asm volatile("v_mov_b32 %0, %1" : "=v"(oz) : "s"(cm.pz));
+  asm volatile("v_mov_b32 %0, %1" : "=v"(dz) : "s"(cm.dz));
+#endif
+  return CamRay{V3{cm.px + ox, cm.py + oy, oz},
+                V3{((cm.lx + s * cm.hx) - cm.px) - ox, ((cm.ly + t * cm.vy) - cm.py) - oy, dz}};
+}
 
 struct KArgs {
   KScene sc;
@@ -855,17 +897,22 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(FR_NUM_SGPR)
           // Camera::get_ray (camera.rs:62-72)
           // scalar loads of the camera from the kernarg segment, here, rather than 19
           // SGPRs held (and spilled) across the loop
-          const KCam cm = kernarg_reload(args, [](const auto& a) { return a.cam; });
-          const V3 cpos{cm.px, cm.py, cm.pz}, cllc{cm.lx, cm.ly, cm.lz}, chor{cm.hx, cm.hy, cm.hz};
-          const V3 cver{cm.vx, cm.vy, cm.vz}, cu{cm.ux, cm.uy, cm.uz}, cv{cm.bx, cm.by, cm.bz};
-          // lens * (k 2^-23) = (lens 2^-23) * k when lens 2^-23 is exact (KCam::lens_pre):
-          // the same product, one rounding
-          const V3 rd = cm.lens_pre ? V3{cm.lens_s * px, cm.lens_s * py, 0.0f}
-                                    : scl(cm.lens, V3{px * kSignedUnitScale, py * kSignedUnitScale, 0.0f});
-          const V3 off = add(scl(rd.x, cu), scl(rd.y, cv));
-          const float u = d.x, v = d.y;
-          o = add(cpos, off);
-          d = sub(sub(add(add(cllc, scl(u, chor)), scl(v, cver)), cpos), off);
+          // An axial camera (every bundled scene's) takes the short form: one scalar branch on
+          // the host's verdict, a run-time fact of the frame (update() moves the camera)
+          KCam cm = kernarg_reload(args, [](const auto& a) { return a.cam; });
+#if defined(__HIP_DEVICE_COMPILE__)
+          // (dz loaded with the rest, ahead of the branch: left to the axial side alone it
+          // became a second scalar load, and a second wait, inside it)
+          asm volatile("" : "+s"(cm.dz));
+#endif
+          const CamLens rd = cam_lens(cm, px, py);
+          CamRay cr;
+          if (cm.lens_pre & kCamAxial)
+            cr = cam_ray_axial(cm, rd, d.x, d.y);
+          else
+            cr = cam_ray(cm, rd, d.x, d.y);
+          o = cr.o;
+          d = cr.d;
           if (!NIB) depth = 0;
           have_ray = true;
         } else {

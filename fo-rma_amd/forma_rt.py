@@ -133,6 +133,7 @@ EXPORTS = (
     "fr_ctx_adapt", "fr_ctx_download_counts", "fr_mctx_adapt",
     "fr_ctx_denoise", "fr_ctx_download_denoised", "fr_ctx_denoised_buffers",
     "fr_ctx_gbuffer", "fr_ctx_download_gbuffer", "fr_ctx_denoise_guided",
+    "fr_camera_axial", "fr_ctx_camera_path", "fr_selftest_camray",
 )
 
 _lib = None
@@ -242,6 +243,10 @@ def lib():
         L.fr_ctx_denoise.argtypes = [vp, C.c_uint32, C.c_float]
         L.fr_ctx_download_denoised.argtypes = [vp, f3, P(C.c_uint8), f3]
         L.fr_ctx_denoised_buffers.argtypes = [vp, P(vp), P(vp)]
+    if hasattr(L, "fr_camera_axial"):  # absent from A/B builds of older sources
+        L.fr_camera_axial.argtypes = [P(FrCamera)]
+        L.fr_ctx_camera_path.argtypes = [vp, P(C.c_int)]
+        L.fr_selftest_camray.argtypes = [C.c_int, P(FrCamera), f3, C.c_uint32, P(C.c_uint32)]
     if hasattr(L, "fr_ctx_gbuffer"):
         L.fr_ctx_gbuffer.argtypes = [vp, vp, P(FrCamera), C.c_uint32, C.c_uint32]
         L.fr_ctx_download_gbuffer.argtypes = [vp, P(C.c_uint32), f3, f3, f3, f3]
@@ -716,6 +721,13 @@ class RenderContext:
         if shape is None:
             raise ForMaError(FR_EARG, "download_error: pass `rel` ([H, W] f32) on a context that rendered elsewhere")
         return shape
+
+    def camera_path(self):
+        """"axial" when the last render (or prepare) generated its camera rays by the short
+        form of an axis-aligned camera, else "general" (fr_ctx_camera_path)."""
+        a = C.c_int(0)
+        check(lib().fr_ctx_camera_path(self._h, C.byref(a)))
+        return "axial" if a.value else "general"
 
     def jit_state(self):
         """FR_JIT_OFF / USED / PENDING / FAILED for the last render (fr_ctx_jit_state)."""

@@ -63,7 +63,8 @@ extern "C" {
                                FR_FLAG_ADAPTIVE, fr_adapt_info, fr_ctx_adapt, fr_ctx_download_counts,
                                fr_mctx_adapt; fr_ctx_denoise, fr_ctx_download_denoised,
                                fr_ctx_denoised_buffers; fr_ctx_gbuffer, fr_ctx_download_gbuffer,
-                               fr_denoise_guide, fr_ctx_denoise_guided) */
+                               fr_denoise_guide, fr_ctx_denoise_guided; fr_camera_axial,
+                               fr_ctx_camera_path, fr_selftest_camray) */
 
 /* error codes */
 #define FR_OK 0
@@ -321,6 +322,19 @@ int fr_ctx_jit_info(fr_ctx* ctx, int* used, double* ms, int* compiled);
 int fr_ctx_jit_state(fr_ctx* ctx, int* state);
 /* Block until no scene-kernel compile is queued or running in this process. */
 int fr_jit_wait(void);
+/* Camera ray form. A camera whose u, v, horizontal and vertical each lie along one axis (every
+   camera fr_camera_init / fr_camera_look builds for an unrotated view) and that passes the
+   zero-sign conditions of DESIGN.md 4.2 has its rays generated by a shorter sequence that
+   gives the same bits. fr_camera_axial: 1 when cam is of that class, 0 when not (host only, no
+   device; FR_EARG for NULL). fr_ctx_camera_path: *axial = 1 when the last render (or
+   fr_ctx_prepare) took the short form; 0 for any other camera, and for every camera while
+   the environment has FR_CAM_GENERAL=1. */
+int fr_camera_axial(const fr_camera* cam);
+int fr_ctx_camera_path(fr_ctx* ctx, int* axial);
+/* Diagnostic: both ray forms on the device for n lens/jitter tuples in[4 i] = (kx, ky, s, t),
+   kx, ky the lens point's integers (2^23-scaled); out[12 i] = the general form's o.xyz, d.xyz,
+   then the short form's, as bit patterns. FR_EARG when cam is not of the axial class. */
+int fr_selftest_camray(int device, const fr_camera* cam, const float* in, uint32_t n, uint32_t* out);
 /* FR_FLAG_ACCUMULATE: the next accumulating frame starts a new accumulation. */
 int fr_ctx_accum_reset(fr_ctx* ctx);
 /* Frames and samples per pixel in the accumulator (0, 0 when there is none). Host-side, as of
