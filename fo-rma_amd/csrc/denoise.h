@@ -294,6 +294,11 @@ hipError_t launch_denoise(hipStream_t stream, const KParams& kp, const float* ac
                           const uint32_t* n_t, const uint32_t* k_t, uint32_t n, uint32_t frames, uint32_t levels,
                           float k, DnPixel* ping, DnPixel* pong, float* mean_rgb, uint8_t* rgb8, float* var);
 
+// The levels alone, on prep's pixels already in ping (fr_ctx_temporal writes its own): `levels`
+// launches ping -> pong -> ping ..., the last one's outputs as launch_denoise's.
+hipError_t launch_denoise_levels(hipStream_t stream, uint32_t width, uint32_t height, uint32_t levels, float k,
+                                 DnPixel* ping, DnPixel* pong, float* mean_rgb, uint8_t* rgb8, float* var);
+
 // The guided filter (fr_ctx_denoise_guided): launch_denoise's arguments, the features g0, g1
 // and alb (W*H float4 each, fr_ctx_gbuffer's) and the guide. The last level's var is the
 // demodulated-space variance the filter steered by.
@@ -306,6 +311,9 @@ hipError_t launch_denoise_guided(hipStream_t stream, const KParams& kp, const fl
                                  uint32_t levels, float k, const DnGuide& guide, const float4* g0, const float4* g1,
                                  const float4* alb, DnPixel* ping, DnPixel* pong, float* mean_rgb, uint8_t* rgb8,
                                  float* var);
+hipError_t launch_denoise_guided_levels(hipStream_t stream, uint32_t width, uint32_t height, uint32_t levels, float k,
+                                        const DnGuide& guide, const float4* g0, const float4* g1, const float4* alb,
+                                        DnPixel* ping, DnPixel* pong, float* mean_rgb, uint8_t* rgb8, float* var);
 
 }  // namespace fr
 #endif

@@ -79,11 +79,19 @@ hipError_t launch_denoise(hipStream_t stream, const KParams& kp, const float* ac
   const uint32_t groups = (kp.P + kSumThreads - 1u) / kSumThreads;
   hipLaunchKernelGGL(denoise_prep_kernel, dim3(groups), dim3(kSumThreads), 0, stream, kp, accum, sq, n_t, k_t, n, frames,
                      reinterpret_cast<float4*>(ping));
-  hipError_t e = hipGetLastError();
-  const dim3 grid((kp.W + kDnTileW - 1u) / kDnTileW, (kp.H + kDnTileH - 1u) / kDnTileH), block(kDnTileW, kDnTileH);
+  const hipError_t e = hipGetLastError();
+  return e != hipSuccess ? e : launch_denoise_levels(stream, kp.W, kp.H, levels, k, ping, pong, mean_rgb, rgb8, var);
+}
+
+hipError_t launch_denoise_levels(hipStream_t stream, uint32_t width, uint32_t height, uint32_t levels, float k,
+                                 DnPixel* ping, DnPixel* pong, float* mean_rgb, uint8_t* rgb8, float* var) {
+  if (!ping || !pong || !mean_rgb || !rgb8 || !var || levels < 1 || levels > kDnLevelsMax) return hipErrorInvalidValue;
+  if (!width || !height) return hipSuccess;
+  hipError_t e = hipSuccess;
+  const dim3 grid((width + kDnTileW - 1u) / kDnTileW, (height + kDnTileH - 1u) / kDnTileH), block(kDnTileW, kDnTileH);
   const float4* in = reinterpret_cast<const float4*>(ping);
   float4* out = reinterpret_cast<float4*>(pong);
-  const int W = static_cast<int>(kp.W), H = static_cast<int>(kp.H);
+  const int W = static_cast<int>(width), H = static_cast<int>(height);
   for (uint32_t i = 0; i < levels && e == hipSuccess; ++i) {
     const int step = 1 << i;
     if (i + 1 == levels)
@@ -175,11 +183,24 @@ hipError_t launch_denoise_guided(hipStream_t stream, const KParams& kp, const fl
   const uint32_t groups = (kp.P + kSumThreads - 1u) / kSumThreads;
   hipLaunchKernelGGL(denoise_prep_guided_kernel, dim3(groups), dim3(kSumThreads), 0, stream, kp, accum, sq, n_t, k_t, n,
                      frames, g0, g1, alb, guide.demodulate, reinterpret_cast<float4*>(ping));
-  hipError_t e = hipGetLastError();
-  const dim3 grid((kp.W + kDnTileW - 1u) / kDnTileW, (kp.H + kDnTileH - 1u) / kDnTileH), block(kDnTileW, kDnTileH);
+  const hipError_t e = hipGetLastError();
+  return e != hipSuccess ? e
+                         : launch_denoise_guided_levels(stream, kp.W, kp.H, levels, k, guide, g0, g1, alb, ping, pong,
+                                                        mean_rgb, rgb8, var);
+}
+
+hipError_t launch_denoise_guided_levels(hipStream_t stream, uint32_t width, uint32_t height, uint32_t levels, float k,
+                                        const DnGuide& guide, const float4* g0, const float4* g1, const float4* alb,
+                                        DnPixel* ping, DnPixel* pong, float* mean_rgb, uint8_t* rgb8, float* var) {
+  if (!ping || !pong || !mean_rgb || !rgb8 || !var || !g0 || !g1 || !alb || levels < 1 || levels > kDnLevelsMax ||
+      guide.normal_pow2 > kDnNormalPow2Max)
+    return hipErrorInvalidValue;
+  if (!width || !height) return hipSuccess;
+  hipError_t e = hipSuccess;
+  const dim3 grid((width + kDnTileW - 1u) / kDnTileW, (height + kDnTileH - 1u) / kDnTileH), block(kDnTileW, kDnTileH);
   const float4* in = reinterpret_cast<const float4*>(ping);
   float4* out = reinterpret_cast<float4*>(pong);
-  const int W = static_cast<int>(kp.W), H = static_cast<int>(kp.H);
+  const int W = static_cast<int>(width), H = static_cast<int>(height);
   for (uint32_t i = 0; i < levels && e == hipSuccess; ++i) {
     const int step = 1 << i;
     if (i + 1 == levels)

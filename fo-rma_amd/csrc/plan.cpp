@@ -285,6 +285,28 @@ int adaptive_step(const AccumState& prev, const TiledState& tiled, const AccumKe
   return FR_OK;
 }
 
+TemporalStep temporal_step(const TemporalState& prev, uint64_t gen, const TemporalKey& key) {
+  TemporalStep s;
+  const bool same = prev.key.scene_uid == key.scene_uid && prev.key.width == key.width &&
+                    prev.key.height == key.height && prev.key.max_depth == key.max_depth;
+  if (prev.has_history && prev.gen == gen && same) {
+    s.action = TemporalAction::kKeep;
+    s.read = prev.read;
+  } else if (prev.has_history && same) {
+    s.action = TemporalAction::kReproject;
+    s.read = prev.read ^ 1u;  // the last view's totals went to the buffer its own reprojection did not read
+  } else {
+    s.action = TemporalAction::kEmpty;
+    s.read = 0;
+  }
+  s.write = s.read ^ 1u;
+  s.next.has_history = true;
+  s.next.key = key;
+  s.next.gen = gen;
+  s.next.read = s.read;
+  return s;
+}
+
 std::string kernel_name(const int t[8]) {
   char name[160];
   auto b = [](int v) { return v ? "true" : "false"; };

@@ -233,6 +233,41 @@ enum class AdaptiveFrame { kTrace, kEmpty };
 // frame then goes through accum_step like any accumulating frame.
 int adaptive_step(const AccumState& prev, const TiledState& tiled, const AccumKey& key, AdaptiveFrame* out);
 
+// ---- temporal reuse (fr_ctx_temporal) --------------------------------
+// A context keeps the totals of the last view fr_ctx_temporal was called for (the history) in
+// one of two buffers and the current accumulation's prior beside them. What a call does is
+// decided by the accumulation generation, a count the driver advances whenever accum_step starts
+// a new accumulation, not by comparing cameras: fr_ctx_accum_reset followed by the same camera
+// reprojects the view's own history.
+struct TemporalKey {  // what must match for a history to be reprojected
+  uint64_t scene_uid = 0;
+  uint32_t width = 0, height = 0, max_depth = 0;
+};
+
+struct TemporalState {
+  bool has_history = false;  // an earlier call's totals stand (false: none yet, dropped, or reset)
+  TemporalKey key;           // the history's
+  uint64_t gen = 0;          // the accumulation generation of the last call
+  uint32_t read = 0;         // the totals buffer that generation's reprojection read; totals go to read ^ 1
+};
+
+enum class TemporalAction {
+  kEmpty,      // no usable history: the prior is all zeros, every reason "no history yet"
+  kKeep,       // the generation of the last call: the prior stands as it is
+  kReproject,  // a new accumulation and a matching history: the prior is reprojected from it
+};
+
+struct TemporalStep {
+  TemporalAction action = TemporalAction::kEmpty;
+  uint32_t read = 0, write = 1;  // totals buffers: the reprojection's source, this call's destination
+  TemporalState next;            // the state once the call is enqueued
+};
+
+// The fr_ctx_temporal call on accumulation generation `gen` seen through `key`: keeps the prior
+// while the generation is that of the last call; reprojects when it changed and the history's
+// scene upload, width, height and max_depth match; drops the history and starts empty otherwise.
+TemporalStep temporal_step(const TemporalState& prev, uint64_t gen, const TemporalKey& key);
+
 // ---- kernel choice ----------------------------------------------------------------
 
 template <int KS_, bool HP_, int KREJ_, int MAXD_, bool BV_, bool MT_, int DEFER_, int MAT_ = 0>

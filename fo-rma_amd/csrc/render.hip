@@ -35,6 +35,7 @@
 #include "pack.h"
 #include "plan.h"
 #include "sum.h"
+#include "temporal.h"
 #include "trace_kernel.h"
 
 namespace fr {
@@ -218,6 +219,30 @@ struct fr_ctx {
   uint64_t gb_uid = 0;
   fr_camera gb_cam{};
   bool gb_valid = false;
+  // fr_ctx_temporal. accum_gen: the accumulation generation, advanced whenever
+  // accum_step starts a new accumulation. d_gb_cls: the G-buffer's scene's effective scatter
+  // classes, gb_n of them, copied with every fr_ctx_gbuffer (the scene's own table dies with an
+  // edit of the scene). Per image pixel, allocated on first use and kept while the size is
+  // unchanged: the totals' two words in two buffers each (tp.read: the one the current prior was
+  // reprojected from; the calls write the other), the history view's G-buffer words and camera,
+  // the prior's two words, the source map and the reason codes. tp_valid: a call was enqueued
+  // since they were (re)allocated; tp_last: the totals buffer it wrote.
+  uint64_t accum_gen = 0;
+  uint32_t* d_gb_cls = nullptr;
+  size_t cap_gb_cls = 0;
+  uint32_t gb_n = 0;
+  float4* d_tp_ta[2] = {nullptr, nullptr};
+  float4* d_tp_tq[2] = {nullptr, nullptr};
+  float4* d_tp_g0 = nullptr;
+  float4* d_tp_g1 = nullptr;
+  float4* d_tp_pa = nullptr;
+  float4* d_tp_pq = nullptr;
+  uint32_t* d_tp_src = nullptr;
+  uint32_t* d_tp_why = nullptr;
+  uint32_t tp_w = 0, tp_h = 0, tp_last = 0;
+  GbCam tp_cam{};
+  TemporalState tp;
+  bool tp_valid = false;
   // the last render was adaptive: the image pixels it traced (fr_stats), or none (empty list)
   bool last_adaptive = false, last_empty = false;
   uint64_t last_active_pixels = 0;
@@ -247,8 +272,9 @@ struct fr_ctx {
   // frames can average the kernel's duration over all of them
   // log 0: trace launches (on the launch's stream); log 1: whole renders (ev0 .. ev1)
   bool log_on = false;
-  std::vector<hipEvent_t> log_ev[2];  // 2 per entry (start, end); reused across logs
-  size_t log_n[2] = {0, 0};           // entries logged
+  // log 2: the three stages of every fr_ctx_temporal call (prior, totals and prep, picture), on the sum stream
+  std::vector<hipEvent_t> log_ev[3];  // 2 per entry (start, end); reused across logs
+  size_t log_n[3] = {0, 0, 0};        // entries logged
 };
 
 static hipError_t log_event(fr_ctx* c, int which, size_t k, hipStream_t st) {
@@ -588,13 +614,17 @@ void fr_ctx_free(fr_ctx* c) {
                   static_cast<void*>(c->d_adapt_sum), static_cast<void*>(c->d_dn_ping),
                   static_cast<void*>(c->d_dn_pong), static_cast<void*>(c->d_dn_mean), static_cast<void*>(c->d_dn_u8),
                   static_cast<void*>(c->d_dn_var), static_cast<void*>(c->d_gb0), static_cast<void*>(c->d_gb1),
-                  static_cast<void*>(c->d_gb_alb)})
+                  static_cast<void*>(c->d_gb_alb), static_cast<void*>(c->d_gb_cls), static_cast<void*>(c->d_tp_ta[0]),
+                  static_cast<void*>(c->d_tp_ta[1]), static_cast<void*>(c->d_tp_tq[0]),
+                  static_cast<void*>(c->d_tp_tq[1]), static_cast<void*>(c->d_tp_g0), static_cast<void*>(c->d_tp_g1),
+                  static_cast<void*>(c->d_tp_pa), static_cast<void*>(c->d_tp_pq), static_cast<void*>(c->d_tp_src),
+                  static_cast<void*>(c->d_tp_why)})
     if (d) (void)hipFree(d);
   for (hipEvent_t e : {c->ev0, c->ev1, c->ev_start, c->ev_copy})
     if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->ev_fslot)
     if (e) (void)hipEventDestroy(e);
-  for (const std::vector<hipEvent_t>* v : {&c->ev_trace, &c->ev_sum, &c->log_ev[0], &c->log_ev[1]})
+  for (const std::vector<hipEvent_t>* v : {&c->ev_trace, &c->ev_sum, &c->log_ev[0], &c->log_ev[1], &c->log_ev[2]})
     for (hipEvent_t e : *v) (void)hipEventDestroy(e);
   for (hipStream_t s : {c->stream2, c->stream_sum, c->stream_copy})
     if (s) (void)hipStreamDestroy(s);
@@ -798,6 +828,7 @@ static int render_impl(fr_ctx* c, fr_scene* scene, const fr_camera* cam, const f
       c->accum = step.next;
       if (!adaptive) c->accum_kp = fp.kp;  // the whole shard's constants (an adaptive frame's are its list's)
       if (step.start) c->tiled = TiledState{};  // a new accumulation is uniform: counts and list are dead
+      if (step.start) ++c->accum_gen;           // (fr_ctx_temporal reprojects once per generation)
     }
     c->last_adaptive = adaptive;
     c->last_empty = false;
@@ -1274,7 +1305,17 @@ int fr_ctx_gbuffer(fr_ctx* c, fr_scene* scene, const fr_camera* cam, uint32_t wi
                  V3{cam->lower_left[0], cam->lower_left[1], cam->lower_left[2]},
                  V3{cam->horizontal[0], cam->horizontal[1], cam->horizontal[2]},
                  V3{cam->vertical[0], cam->vertical[1], cam->vertical[2]}};
+  // fr_ctx_temporal's cap reads the hit primitive's class: a copy the context owns (the scene's
+  // table is freed by the scene's next edit, which hipFree orders behind this copy)
+  const size_t cls_bytes = static_cast<size_t>(gs.n) * sizeof(uint32_t);
+  if (c->cap_gb_cls < cls_bytes) {
+    HIPCHK(hipStreamSynchronize(c->stream_sum));  // a reprojection may read the smaller table
+    c->gb_valid = false;
+    if ((rc = grow(c->d_gb_cls, c->cap_gb_cls, cls_bytes))) return rc;
+  }
   HIPCHK(launch_gbuffer(c->stream_sum, gs, gc, width, height, c->d_gb0, c->d_gb1, c->d_gb_alb));
+  if (cls_bytes) HIPCHK(hipMemcpyAsync(c->d_gb_cls, gs.cls, cls_bytes, hipMemcpyDeviceToDevice, c->stream_sum));
+  c->gb_n = gs.n;
   c->gb_uid = dc->uid;
   c->gb_cam = *cam;
   c->gb_valid = true;
@@ -1304,15 +1345,8 @@ int fr_ctx_download_gbuffer(fr_ctx* c, uint32_t* prim, float* depth, float* norm
   return FR_OK;
 }
 
-// The guided filter on demand (DESIGN.md §4.5e): fr_ctx_denoise's place on the sum stream, behind
-// the G-buffer pass it reads (the same stream), into the same output buffers.
-int fr_ctx_denoise_guided(fr_ctx* c, uint32_t levels, float k, const fr_denoise_guide* g) {
-  if (!c) return set_error(FR_EARG, "fr_ctx_denoise_guided: null ctx");
-  static const char* who = "fr_ctx_denoise_guided";
-  int rc;
-  if ((rc = denoise_refusal(c, who, levels, k))) return rc;
-  const fr_denoise_guide dflt{kDnSigmaZDefault, kDnNormalPow2Default, 1u, 0u};
-  const fr_denoise_guide gd = g ? *g : dflt;
+// A guide field out of range, as fr_ctx_denoise_guided and fr_ctx_temporal (`who`) refuse it.
+static int guide_refusal(const char* who, const fr_denoise_guide& gd) {
   if (!(gd.sigma_z > 0.0f && gd.sigma_z <= kDnSigmaZMax))
     return set_error(FR_EARG, "%s: sigma_z %g must be finite, > 0 and <= %g", who, static_cast<double>(gd.sigma_z),
                      static_cast<double>(kDnSigmaZMax));
@@ -1320,6 +1354,12 @@ int fr_ctx_denoise_guided(fr_ctx* c, uint32_t levels, float k, const fr_denoise_
     return set_error(FR_EARG, "%s: normal_pow2 %u must be 0 to %u", who, gd.normal_pow2, kDnNormalPow2Max);
   if (gd.demodulate > 1u) return set_error(FR_EARG, "%s: demodulate %u must be 0 or 1", who, gd.demodulate);
   if (gd.pad != 0u) return set_error(FR_EARG, "%s: pad %u must be 0", who, gd.pad);
+  return FR_OK;
+}
+
+// What fr_ctx_denoise_guided and fr_ctx_temporal (`who`) refuse alike of the G-buffer: none, or one
+// of another scene upload, camera or size than the live accumulation's.
+static int gbuffer_refusal(const fr_ctx* c, const char* who) {
   if (!c->gb_valid) return set_error(FR_EARG, "%s: no G-buffer (fr_ctx_gbuffer first)", who);
   const AccumState& a = c->accum;
   const KParams& kp = c->accum_kp;
@@ -1331,6 +1371,22 @@ int fr_ctx_denoise_guided(fr_ctx* c, uint32_t levels, float k, const fr_denoise_
     return set_error(FR_EARG, "%s: the G-buffer's width %u differs from the live accumulation's %u", who, c->gb_w, kp.W);
   if (c->gb_h != kp.H)
     return set_error(FR_EARG, "%s: the G-buffer's height %u differs from the live accumulation's %u", who, c->gb_h, kp.H);
+  return FR_OK;
+}
+
+// The guided filter on demand (DESIGN.md §4.5e): fr_ctx_denoise's place on the sum stream, behind
+// the G-buffer pass it reads (the same stream), into the same output buffers.
+int fr_ctx_denoise_guided(fr_ctx* c, uint32_t levels, float k, const fr_denoise_guide* g) {
+  if (!c) return set_error(FR_EARG, "fr_ctx_denoise_guided: null ctx");
+  static const char* who = "fr_ctx_denoise_guided";
+  int rc;
+  if ((rc = denoise_refusal(c, who, levels, k))) return rc;
+  const fr_denoise_guide dflt{kDnSigmaZDefault, kDnNormalPow2Default, 1u, 0u};
+  const fr_denoise_guide gd = g ? *g : dflt;
+  if ((rc = guide_refusal(who, gd))) return rc;
+  if ((rc = gbuffer_refusal(c, who))) return rc;
+  const AccumState& a = c->accum;
+  const KParams& kp = c->accum_kp;
   SET_DEVICE(c->device);
   if ((rc = denoise_buffers(c))) return rc;
   const bool tiled = c->tiled.tiled;
@@ -1360,6 +1416,183 @@ int fr_ctx_denoised_buffers(fr_ctx* c, float** d_mean_rgb, uint8_t** d_rgb8) {
   if (!c->dn_valid) return set_error(FR_EARG, "fr_ctx_denoised_buffers: no denoised image (fr_ctx_denoise first)");
   if (d_mean_rgb) *d_mean_rgb = c->d_dn_mean;
   if (d_rgb8) *d_rgb8 = c->d_dn_u8;
+  return FR_OK;
+}
+
+// ---- temporal reuse -----------------------------------------------------
+
+static_assert(sizeof(fr_temporal) == 32, "fr_temporal layout");
+
+// The history's and the prior's buffers at the live accumulation's size. Another size loses the
+// history with its buffers.
+static int temporal_buffers(fr_ctx* c) {
+  const KParams& kp = c->accum_kp;
+  if (c->tp_w == kp.W && c->tp_h == kp.H && c->d_tp_why) return FR_OK;
+  HIPCHK(hipStreamSynchronize(c->stream_sum));  // the kernels and copies that use the old buffers
+  c->tp_valid = false;
+  c->tp = TemporalState{};
+  c->tp_w = c->tp_h = 0;
+  const size_t px = static_cast<size_t>(kp.W) * kp.H;
+  int rc;
+  for (float4** b : {&c->d_tp_ta[0], &c->d_tp_ta[1], &c->d_tp_tq[0], &c->d_tp_tq[1], &c->d_tp_g0, &c->d_tp_g1,
+                     &c->d_tp_pa, &c->d_tp_pq}) {
+    size_t cap = 0;  // (grow with no capacity: each buffer is replaced)
+    if ((rc = grow(*b, cap, px * sizeof(float4)))) return rc;
+  }
+  for (uint32_t** b : {&c->d_tp_src, &c->d_tp_why}) {
+    size_t cap = 0;
+    if ((rc = grow(*b, cap, px * sizeof(uint32_t)))) return rc;
+  }
+  c->tp_w = kp.W;
+  c->tp_h = kp.H;
+  return FR_OK;
+}
+
+static GbCam gb_cam_of(const fr_camera& cam) {
+  return GbCam{V3{cam.position[0], cam.position[1], cam.position[2]},
+               V3{cam.lower_left[0], cam.lower_left[1], cam.lower_left[2]},
+               V3{cam.horizontal[0], cam.horizontal[1], cam.horizontal[2]},
+               V3{cam.vertical[0], cam.vertical[1], cam.vertical[2]}};
+}
+
+// Everything a call enqueues, on the sum stream: behind the resolve of every frame enqueued so
+// far and behind the G-buffer pass, ahead of every later frame's resolve.
+static int temporal_enqueue(fr_ctx* c, const TemporalStep& st, uint32_t levels, float k, const fr_denoise_guide* g,
+                            const TpOpt& opt) {
+  const KParams& kp = c->accum_kp;
+  const AccumState& a = c->accum;
+  hipStream_t s = c->stream_sum;
+  const size_t px = static_cast<size_t>(kp.W) * kp.H;
+  const bool log = c->log_on;  // fr_ctx_trace_log: an event pair around each of the three stages
+  if (log) HIPCHK(log_start(c, 2, s));
+  if (st.action == TemporalAction::kReproject)
+    HIPCHK(launch_temporal_reproject(s, tp_cam(c->tp_cam), opt, kp.W, kp.H, c->d_gb0, c->d_gb1, c->d_gb_cls, c->gb_n,
+                                     c->d_tp_g0, c->d_tp_g1, c->d_tp_ta[st.read], c->d_tp_tq[st.read], c->d_tp_pa,
+                                     c->d_tp_pq, c->d_tp_src, c->d_tp_why));
+  if (st.action == TemporalAction::kEmpty && px) {
+    HIPCHK(hipMemsetAsync(c->d_tp_pa, 0, px * sizeof(float4), s));
+    HIPCHK(hipMemsetAsync(c->d_tp_pq, 0, px * sizeof(float4), s));
+    HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c->d_tp_src), static_cast<int>(kTpNone), px, s));
+    HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c->d_tp_why), static_cast<int>(kTpNoHistory), px, s));
+  }
+  if (st.action != TemporalAction::kKeep && px) {
+    // the view's own G-buffer words join its history, behind the reprojection that read the last view's
+    HIPCHK(hipMemcpyAsync(c->d_tp_g0, c->d_gb0, px * sizeof(float4), hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(c->d_tp_g1, c->d_gb1, px * sizeof(float4), hipMemcpyDeviceToDevice, s));
+  }
+  if (log) HIPCHK(log_end(c, 2, s));
+  if (log) HIPCHK(log_start(c, 2, s));
+  const bool tiled = c->tiled.tiled;
+  HIPCHK(launch_temporal_prep(s, kp, c->d_accum, c->d_sq, tiled ? c->d_nt : nullptr, tiled ? c->d_kt : nullptr,
+                              a.samples, a.frames, c->d_tp_pa, c->d_tp_pq, c->d_tp_ta[st.write], c->d_tp_tq[st.write],
+                              g ? c->d_gb0 : nullptr, c->d_gb1, g ? c->d_gb_alb : nullptr,
+                              g ? g->demodulate : 0u, c->d_dn_ping));
+  if (log) HIPCHK(log_end(c, 2, s));
+  if (log) HIPCHK(log_start(c, 2, s));
+  if (levels == 0)
+    HIPCHK(launch_temporal_finalise(s, kp.W, kp.H, c->d_dn_ping, g ? c->d_gb_alb : nullptr, g ? g->demodulate : 0u,
+                                    c->d_dn_mean, c->d_dn_u8, c->d_dn_var));
+  else if (g)
+    HIPCHK(launch_denoise_guided_levels(s, kp.W, kp.H, levels, k, DnGuide{g->sigma_z, g->normal_pow2, g->demodulate},
+                                        c->d_gb0, c->d_gb1, c->d_gb_alb, c->d_dn_ping, c->d_dn_pong, c->d_dn_mean,
+                                        c->d_dn_u8, c->d_dn_var));
+  else
+    HIPCHK(launch_denoise_levels(s, kp.W, kp.H, levels, k, c->d_dn_ping, c->d_dn_pong, c->d_dn_mean, c->d_dn_u8,
+                                 c->d_dn_var));
+  if (log) HIPCHK(log_end(c, 2, s));
+  return FR_OK;
+}
+
+// Temporal reuse on demand: fr_ctx_denoise's place on the sum stream and its output buffers;
+// nothing is waited for. A, Q, the counts, d_mean, d_u8, the pending render and its stats are read
+// or untouched. Within one accumulation the prior stands: a later call's opt does not change it.
+int fr_ctx_temporal(fr_ctx* c, uint32_t levels, float k, const fr_denoise_guide* g, const fr_temporal* opt) {
+  if (!c) return set_error(FR_EARG, "fr_ctx_temporal: null ctx");
+  static const char* who = "fr_ctx_temporal";
+  if (levels > kDnLevelsMax) return set_error(FR_EARG, "%s: levels %u must be 0 to %u", who, levels, kDnLevelsMax);
+  if (!(k > 0.0f && k <= kDnKMax))
+    return set_error(FR_EARG, "%s: k %g must be finite, > 0 and <= %g", who, static_cast<double>(k),
+                     static_cast<double>(kDnKMax));
+  const AccumState& a = c->accum;
+  if (!a.live) return set_error(FR_EARG, "%s: no live accumulation (no FR_FLAG_ACCUMULATE frame yet, or reset)", who);
+  if (!a.has_q || !c->d_sq)
+    return set_error(FR_EARG, "%s: the live accumulation carries no Q: its frames lack FR_FLAG_ACCUM_ERROR", who);
+  if (c->accum_kp.shard_count != 1)
+    return set_error(FR_EARG, "%s: shard_count %u: a reprojected pixel's source lies in the strips of other shards, "
+                              "only a whole image (shard_count 1) is reused", who, c->accum_kp.shard_count);
+  int rc;
+  if (g && (rc = guide_refusal(who, *g))) return rc;
+  const fr_temporal dflt{kTpNMaxDefault, kTpNMaxSpecularDefault, kTpSigmaZDefault, kTpNormalMinDefault, {0u, 0u, 0u, 0u}};
+  const fr_temporal o = opt ? *opt : dflt;
+  if (!(o.n_max > 0.0f && o.n_max <= kTpNMaxMax))
+    return set_error(FR_EARG, "%s: n_max %g must be finite, > 0 and <= %g", who, static_cast<double>(o.n_max),
+                     static_cast<double>(kTpNMaxMax));
+  if (!(o.n_max_specular >= 0.0f && o.n_max_specular <= kTpNMaxMax))
+    return set_error(FR_EARG, "%s: n_max_specular %g must be finite, >= 0 and <= %g", who,
+                     static_cast<double>(o.n_max_specular), static_cast<double>(kTpNMaxMax));
+  if (!(o.sigma_z > 0.0f && o.sigma_z <= kDnSigmaZMax))
+    return set_error(FR_EARG, "%s: temporal sigma_z %g must be finite, > 0 and <= %g", who,
+                     static_cast<double>(o.sigma_z), static_cast<double>(kDnSigmaZMax));
+  if (!(o.normal_min >= -1.0f && o.normal_min <= 1.0f))
+    return set_error(FR_EARG, "%s: normal_min %g must be finite, >= -1 and <= 1", who, static_cast<double>(o.normal_min));
+  for (uint32_t p : o.pad)
+    if (p != 0u) return set_error(FR_EARG, "%s: temporal pad %u must be 0", who, p);
+  if ((rc = gbuffer_refusal(c, who))) return rc;
+  SET_DEVICE(c->device);
+  if ((rc = denoise_buffers(c))) return rc;
+  if ((rc = temporal_buffers(c))) return rc;
+  const TemporalStep st =
+      temporal_step(c->tp, c->accum_gen, TemporalKey{a.key.scene_uid, a.key.width, a.key.height, a.key.max_depth});
+  if ((rc = temporal_enqueue(c, st, levels, k, g, TpOpt{o.n_max, o.n_max_specular, o.sigma_z, o.normal_min}))) {
+    c->tp = TemporalState{};  // part of a call may stand on the device: the history is not to be trusted
+    c->tp_valid = false;
+    return rc;
+  }
+  c->tp = st.next;
+  if (st.action != TemporalAction::kKeep) c->tp_cam = gb_cam_of(a.key.cam);
+  c->tp_last = st.write;
+  c->tp_valid = true;
+  c->dn_valid = true;
+  return FR_OK;
+}
+
+int fr_ctx_temporal_reset(fr_ctx* c) {
+  if (!c) return set_error(FR_EARG, "fr_ctx_temporal_reset: null ctx");
+  c->tp = TemporalState{};  // (host state only: the next call's prior is filled afresh)
+  return FR_OK;
+}
+
+int fr_ctx_download_temporal(fr_ctx* c, float* prior_a, float* prior_q, float* prior_n, float* prior_k, float* total_a,
+                             float* total_q, float* total_n, float* total_k, uint32_t* source, uint32_t* reason) {
+  if (!c) return set_error(FR_EARG, "fr_ctx_download_temporal: null ctx");
+  if (!c->tp_valid) return set_error(FR_EARG, "fr_ctx_download_temporal: no temporal call (fr_ctx_temporal first)");
+  SET_DEVICE(c->device);
+  const size_t px = static_cast<size_t>(c->tp_w) * c->tp_h;
+  hipStream_t st = c->stream_sum;
+  // the device words are unpacked on the host: only the planes asked for are copied
+  struct Plane {
+    const float4* dev;
+    float *rgb, *w;
+    std::vector<float> host;
+  } planes[4] = {{c->d_tp_pa, prior_a, prior_n, {}},
+                 {c->d_tp_pq, prior_q, prior_k, {}},
+                 {c->d_tp_ta[c->tp_last], total_a, total_n, {}},
+                 {c->d_tp_tq[c->tp_last], total_q, total_k, {}}};
+  for (Plane& p : planes) {
+    if (!(p.rgb || p.w) || !px) continue;
+    p.host.resize(4 * px);
+    HIPCHK(hipMemcpyAsync(p.host.data(), p.dev, px * sizeof(float4), hipMemcpyDeviceToHost, st));
+  }
+  if (source && px) HIPCHK(hipMemcpyAsync(source, c->d_tp_src, px * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  if (reason && px) HIPCHK(hipMemcpyAsync(reason, c->d_tp_why, px * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  for (Plane& p : planes) {
+    if (p.host.empty()) continue;
+    for (size_t i = 0; i < px; ++i) {
+      if (p.rgb) memcpy(&p.rgb[3 * i], &p.host[4 * i], 12);
+      if (p.w) p.w[i] = p.host[4 * i + 3];
+    }
+  }
   return FR_OK;
 }
 
@@ -1424,24 +1657,25 @@ int fr_ctx_trace_log(fr_ctx* c, int enable) {
     HIPCHK(hipStreamSynchronize(c->stream));
     HIPCHK(hipStreamSynchronize(c->stream2));
     HIPCHK(hipStreamSynchronize(c->stream_sum));
-    c->log_n[0] = c->log_n[1] = 0;
+    c->log_n[0] = c->log_n[1] = c->log_n[2] = 0;
   }
   c->log_on = enable != 0;
   return FR_OK;
 }
 
 int fr_ctx_trace_log_read(fr_ctx* c, int which, double* ms, uint32_t cap, uint32_t* n) {
-  if (!c || !n || which < 0 || which > 3) return set_error(FR_EARG, "fr_ctx_trace_log_read: bad argument");
+  if (!c || !n || which < 0 || which > 4) return set_error(FR_EARG, "fr_ctx_trace_log_read: bad argument");
   SET_DEVICE(c->device);
   HIPCHK(hipStreamSynchronize(c->stream));
   HIPCHK(hipStreamSynchronize(c->stream2));
   HIPCHK(hipStreamSynchronize(c->stream_sum));  // a pipelined render's end event is recorded there
   // which 0 / 1: durations of the trace launches / renders; 2 / 3: their start and end times
-  // (two values each) from the first logged trace launch's start (a timeline)
-  const int w = which & 1;
+  // (two values each) from the first logged trace launch's start (a timeline); 4: durations of
+  // the stages of the fr_ctx_temporal calls, three entries per call
+  const int w = which == 4 ? 2 : which & 1;
   *n = static_cast<uint32_t>(c->log_n[w]);
   for (size_t i = 0; i < c->log_n[w] && ms; ++i) {
-    if (which < 2) {
+    if (which < 2 || which == 4) {
       if (i >= cap) break;
       float t = 0.0f;
       HIPCHK(hipEventElapsedTime(&t, c->log_ev[w][2 * i], c->log_ev[w][2 * i + 1]));

@@ -50,6 +50,12 @@ FR_DN_EPS, FR_DN_MEAN_MAX, FR_DN_VAR_MAX = 2.0 ** -20, 2.0 ** 40, 2.0 ** 80
 FR_GBUFFER_MISS = 0xFFFFFFFF
 FR_DN_FEAT_MAX, FR_DN_NORMAL_MAX, FR_DN_ALB_MIN, FR_DN_ALB_MAX = 2.0 ** 40, 2.0 ** 10, 2.0 ** -6, 2.0 ** 6
 FR_DN_SIGMA_Z_DEFAULT, FR_DN_NORMAL_POW2_DEFAULT = 2.0 ** -5, 4
+# fr_ctx_temporal (forma_rt.h): the source map's "none", the reason codes, the defaults
+FR_TP_NONE = 0xFFFFFFFF
+(FR_TP_REUSED, FR_TP_NO_HISTORY, FR_TP_MISS, FR_TP_OFFSCREEN, FR_TP_ID, FR_TP_NORMAL, FR_TP_PLANE,
+ FR_TP_HISTORY) = range(8)
+FR_TP_N_MAX_DEFAULT, FR_TP_N_MAX_SPECULAR_DEFAULT, FR_TP_N_MAX_MAX = 32.0, 4.0, 2.0 ** 24
+FR_TP_SIGMA_Z_DEFAULT, FR_TP_NORMAL_MIN_DEFAULT = 2.0 ** -5, float(np.float32(0.9))
 FR_JIT_OFF, FR_JIT_USED, FR_JIT_PENDING, FR_JIT_FAILED, FR_JIT_MISS = 0, 1, 2, 3, 4  # fr_ctx_jit_state
 MAX_DEPTH = 50  # tracer.rs:10
 DEFAULT_SEED = 0x5EED
@@ -114,6 +120,11 @@ class FrDenoiseGuide(C.Structure):
     _fields_ = [("sigma_z", C.c_float), ("normal_pow2", C.c_uint32), ("demodulate", C.c_uint32), ("pad", C.c_uint32)]
 
 
+class FrTemporal(C.Structure):
+    _fields_ = [("n_max", C.c_float), ("n_max_specular", C.c_float), ("sigma_z", C.c_float), ("normal_min", C.c_float),
+                ("pad", C.c_uint32 * 4)]
+
+
 # Every symbol include/forma_rt.h declares (checked by tests/test_abi.py).
 EXPORTS = (
     "fr_last_error", "fr_abi_version", "fr_device_count",
@@ -134,6 +145,7 @@ EXPORTS = (
     "fr_ctx_denoise", "fr_ctx_download_denoised", "fr_ctx_denoised_buffers",
     "fr_ctx_gbuffer", "fr_ctx_download_gbuffer", "fr_ctx_denoise_guided",
     "fr_camera_axial", "fr_ctx_camera_path", "fr_selftest_camray",
+    "fr_ctx_temporal", "fr_ctx_temporal_reset", "fr_ctx_download_temporal",
 )
 
 _lib = None
@@ -251,6 +263,10 @@ def lib():
         L.fr_ctx_gbuffer.argtypes = [vp, vp, P(FrCamera), C.c_uint32, C.c_uint32]
         L.fr_ctx_download_gbuffer.argtypes = [vp, P(C.c_uint32), f3, f3, f3, f3]
         L.fr_ctx_denoise_guided.argtypes = [vp, C.c_uint32, C.c_float, P(FrDenoiseGuide)]
+    if hasattr(L, "fr_ctx_temporal"):
+        L.fr_ctx_temporal.argtypes = [vp, C.c_uint32, C.c_float, P(FrDenoiseGuide), P(FrTemporal)]
+        L.fr_ctx_temporal_reset.argtypes = [vp]
+        L.fr_ctx_download_temporal.argtypes = [vp] + [f3] * 8 + [P(C.c_uint32)] * 2
     _lib = L
     return L
 
@@ -716,6 +732,51 @@ class RenderContext:
         check(lib().fr_ctx_denoised_buffers(self._h, C.byref(dm), C.byref(du)))
         return dm.value, du.value
 
+    def temporal(self, levels=FR_DN_LEVELS_DEFAULT, k=FR_DN_K_DEFAULT, guide=None, n_max=FR_TP_N_MAX_DEFAULT,
+                 n_max_specular=FR_TP_N_MAX_SPECULAR_DEFAULT, sigma_z=FR_TP_SIGMA_Z_DEFAULT,
+                 normal_min=FR_TP_NORMAL_MIN_DEFAULT):
+        """Enqueues temporal reuse of the live accumulation (fr_ctx_temporal: frames of
+        make_params(accumulate="error") or "adaptive", one or more, shard_count 1, and the
+        gbuffer() of the same scene, camera and size) and returns at once. On the first call of
+        a new accumulation the previous view's totals are reprojected into a per-pixel prior
+        (n_max / n_max_specular cap its samples, sigma_z and normal_min accept a source); every
+        call adds the prior to the accumulation, keeps the totals as the view's history and
+        shows them: levels 0 as they are, 1 to 6 through denoise()'s levels with scale k.
+        guide: None for the unguided levels, True for the guided ones at their defaults, or a
+        dict of denoise()'s sigma_z, normal_pow2 and demodulate. The results land in denoise()'s
+        buffers (download_denoised)."""
+        g = None
+        if guide is not None and guide is not False:
+            kw = {} if guide is True else dict(guide)
+            g = FrDenoiseGuide(float(kw.pop("sigma_z", FR_DN_SIGMA_Z_DEFAULT)),
+                               int(kw.pop("normal_pow2", FR_DN_NORMAL_POW2_DEFAULT)), int(kw.pop("demodulate", True)), 0)
+            if kw:
+                raise TypeError(f"guide: unknown keys {sorted(kw)}")
+        o = FrTemporal(float(n_max), float(n_max_specular), float(sigma_z), float(normal_min))
+        check(lib().fr_ctx_temporal(self._h, int(levels), float(k), C.byref(g) if g is not None else None, C.byref(o)))
+
+    def temporal_reset(self):
+        """Drops the temporal history: the next temporal() starts with an empty prior."""
+        check(lib().fr_ctx_temporal_reset(self._h))
+
+    def download_temporal(self, width, height):
+        """The last temporal() as a dict: "prior_a", "prior_q", "total_a", "total_q" [H, W, 3] f32,
+        "prior_n", "prior_k", "total_n", "total_k" [H, W] f32, "source" [H, W] uint32 (y0 W + x0 or
+        FR_TP_NONE) and "reason" [H, W] uint32 (FR_TP_*). Waits for it."""
+        out = {}
+        for kind in ("prior", "total"):
+            for name, shape in (("a", (height, width, 3)), ("q", (height, width, 3)), ("n", (height, width)),
+                                ("k", (height, width))):
+                out[f"{kind}_{name}"] = np.full(shape, np.nan, dtype=np.float32)
+        out["source"] = np.zeros((height, width), dtype=np.uint32)
+        out["reason"] = np.zeros((height, width), dtype=np.uint32)
+        fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))  # noqa: E731
+        up = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint32))  # noqa: E731
+        check(lib().fr_ctx_download_temporal(
+            self._h, *[fp(out[f"{kind}_{name}"]) for kind in ("prior", "total") for name in ("a", "q", "n", "k")],
+            up(out["source"]), up(out["reason"])))
+        return out
+
     def _err_shape(self):
         shape = getattr(self, "_accum_shape", None)
         if shape is None:
@@ -739,11 +800,13 @@ class RenderContext:
         """Start (or stop) logging every trace-kernel launch's HIP-event duration."""
         check(lib().fr_ctx_trace_log(self._h, 1 if enable else 0))
 
-    def trace_log_read(self, frames=False, timeline=False):
+    def trace_log_read(self, frames=False, timeline=False, temporal=False):
         """HIP-event durations (ms) logged since trace_log(True): every trace-kernel launch,
         or (frames=True) every whole render (trace + sum kernels). timeline=True: (start, end)
-        pairs instead, in ms from the first logged trace launch's start."""
-        which = (1 if frames else 0) + (2 if timeline else 0)
+        pairs instead, in ms from the first logged trace launch's start. temporal=True: the
+        stages of every temporal() call, three durations per call: the prior, totals and prep,
+        the picture."""
+        which = 4 if temporal else (1 if frames else 0) + (2 if timeline else 0)
         n = C.c_uint32(0)
         check(lib().fr_ctx_trace_log_read(self._h, which, None, 0, C.byref(n)))
         k = 2 if timeline else 1
@@ -938,6 +1001,9 @@ def post_process(rgba, effects, time=0.0, device=0):
 
 # ---- tracer.rs operator API ---------------------------------------------------
 
+_DENOISE_MODES = (False, True, "guided", "temporal", "temporal-guided")
+
+
 class TraceModel:
     """tracer.rs:12-17 {scene, width, height, pixels}, plus the render context the frames
     run on: one fr_ctx per model, created on the first frame and reused by every later
@@ -980,9 +1046,12 @@ class TraceModel:
         accumulate "error" or "adaptive"): from the second frame of an accumulation on the image
         is the accumulation's denoised u8 (RenderContext.denoise at the defaults); on its first
         frame, which has no variance yet, the plain u8. denoise="guided": the feature-guided
-        filter at its defaults; the view's G-buffer is enqueued when an accumulation starts."""
-        if denoise not in (False, True, "guided"):
-            raise ValueError(f'denoise={denoise!r}: False, True or "guided"')
+        filter at its defaults; the view's G-buffer is enqueued when an accumulation starts.
+        denoise="temporal" / "temporal-guided": RenderContext.temporal at its defaults (with the
+        guided levels), from the first frame on: a moved camera's first frame shows the previous
+        view's accumulation reprojected under it."""
+        if denoise not in _DENOISE_MODES:
+            raise ValueError(f'denoise={denoise!r}: False, True or "guided", "temporal", "temporal-guided"')
         if denoise and accumulate not in ("error", "adaptive"):
             raise ValueError(f'denoise={denoise!r} needs accumulate="error" or "adaptive": the filter is steered by '
                              "the accumulation's variance")
@@ -992,10 +1061,14 @@ class TraceModel:
         self.last_stats = ctx.sync()
         if self._pinned is None:
             self._pinned = PinnedFrame(self.width, self.height)
-        guided = denoise == "guided"
-        if guided and ctx.accum_info()[0] == 1:  # a new accumulation: a new view
+        guided = denoise in ("guided", "temporal-guided")
+        temporal = denoise in ("temporal", "temporal-guided")
+        if (guided or temporal) and ctx.accum_info()[0] == 1:  # a new accumulation: a new view
             ctx.gbuffer(scene, self.scene.camera, self.width, self.height)
-        if denoise and ctx.accum_info()[0] >= 2:
+        if temporal:
+            ctx.temporal(guide=guided or None)
+            ctx.download_denoised_into(self._pinned.u8)
+        elif denoise and ctx.accum_info()[0] >= 2:
             ctx.denoise(guided=guided)
             ctx.download_denoised_into(self._pinned.u8)
         else:
@@ -1034,9 +1107,11 @@ def update(model, keys, delta_time, max_depth=MAX_DEPTH, accumulate=False, denoi
     per-pixel variance (RenderContext.denoise) from its second frame on, the plain picture on
     its first frame and right after a key press restarts it. denoise="guided": the same with the
     feature-guided filter (RenderContext.denoise(guided=True)), whose G-buffer is enqueued on the
-    first frame of each accumulation."""
-    if denoise not in (False, True, "guided"):
-        raise ValueError(f'denoise={denoise!r}: False, True or "guided"')
+    first frame of each accumulation. denoise="temporal": temporal reuse (RenderContext.temporal)
+    from the first frame of every accumulation on, so the frames shown while a key is held carry
+    the previous view's samples; "temporal-guided": the same through the guided levels."""
+    if denoise not in _DENOISE_MODES:
+        raise ValueError(f'denoise={denoise!r}: False, True or "guided", "temporal", "temporal-guided"')
     if denoise and accumulate not in ("error", "adaptive"):
         raise ValueError(f'denoise={denoise!r} needs accumulate="error" or "adaptive"')
     d = (C.c_float * 3)()

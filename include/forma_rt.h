@@ -64,7 +64,8 @@ extern "C" {
                                fr_mctx_adapt; fr_ctx_denoise, fr_ctx_download_denoised,
                                fr_ctx_denoised_buffers; fr_ctx_gbuffer, fr_ctx_download_gbuffer,
                                fr_denoise_guide, fr_ctx_denoise_guided; fr_camera_axial,
-                               fr_ctx_camera_path, fr_selftest_camray) */
+                               fr_ctx_camera_path, fr_selftest_camray; fr_temporal,
+                               fr_ctx_temporal, fr_ctx_temporal_reset, fr_ctx_download_temporal) */
 
 /* error codes */
 #define FR_OK 0
@@ -304,7 +305,10 @@ int fr_ctx_device_buffers(fr_ctx* ctx, float** d_mean_rgb, uint8_t** d_rgb8);
    the whole render (trace + sum kernels). _read waits for the logged work and writes up
    to cap durations (ms) in order: which = 0 the trace launches, 1 the renders; which = 2
    / 3 the same entries as (start, end) pairs in ms from the first logged trace launch's
-   start (2 values per entry, a timeline); *n = the entries logged. Lets a caller
+   start (2 values per entry, a timeline); which = 4 the stages of every fr_ctx_temporal call,
+   three entries per call in order: the prior (reprojection and the copy of the view's G-buffer
+   words, or the fills of an empty prior; nothing when the prior is kept), totals and prep, the
+   picture (the levels, or the finalise kernel); *n = the entries logged. Lets a caller
    streaming K frames average all K of them and see the gaps between them. */
 int fr_ctx_trace_log(fr_ctx* ctx, int enable);
 int fr_ctx_trace_log_read(fr_ctx* ctx, int which, double* ms, uint32_t cap, uint32_t* n);
@@ -485,6 +489,75 @@ typedef struct fr_denoise_guide {
    upload, camera, width or height differs from the live accumulation's (fr_last_error says
    which). */
 int fr_ctx_denoise_guided(fr_ctx* ctx, uint32_t levels, float k, const fr_denoise_guide* guide);
+
+/* Temporal reuse: the live accumulation of the current view plus the accumulators of the
+   previous view, reprojected per pixel through the G-buffers of both views (the temporal part
+   of SVGF; fr_ctx_denoise's levels are the spatial part). Only the camera moves: a scene edit
+   drops the history. Every operation rounds once in f32 (fo-rma_amd/csrc/temporal.h).
+   History of a view: per image pixel the totals (A_T[3], Q_T[3], n_T, K_T), n_T and K_T in f32,
+   as of the view's last fr_ctx_temporal call, with that view's G-buffer and camera.
+   Reprojection, once, on the first call after a new accumulation started (an accumulating frame
+   that did not continue the one before: another camera, or fr_ctx_accum_reset and the same camera,
+   which reuses the view's own history). For a pixel with features (N, t, P, id):
+     a miss has no history;
+     q = P - pos0, e = ll0 - pos0, nrm = cross(hor0, ver0), hh = dot(hor0, hor0), vv = dot(ver0, ver0)
+     (the previous camera; nrm, hh, vv once on the host), s = dot(e, nrm) / dot(q, nrm),
+     r = s q - e, u = dot(r, hor0) / hh, v = dot(r, ver0) / vv, fx = floor(u W), fy = floor(v H);
+     valid iff s > 0, 0 <= fx < W and 1 <= fy <= H, compared on the floats (NaN fails); the source
+     pixel is (fx, H - fy): fr_ctx_gbuffer's primary ray inverted. The fetch is nearest-pixel.
+     The source is accepted iff its id equals id, dot(N, N0) >= normal_min, d d <= z z + FR_DN_EPS
+     with d = dot(N, P0 - P) and z = sigma_z t, and its totals have n_T > 0 and finite A_T, Q_T
+     (tested in this order; the first failure is the pixel's reason).
+     cap = n_max, or n_max_specular if the primitive's scatter class is metal or dielectric;
+     f = n_T > cap ? cap / n_T : 1; the prior is A' = A_T f, Q' = Q_T f, n' = n_T f,
+     K' = 1 + (K_T - 1) f. f = 0 (a cap of 0) and every rejected pixel: a prior of all zeros.
+   While the accumulation goes on, later calls keep the prior's bits. Without a history (first
+   view, fr_ctx_temporal_reset, another scene upload, size or max_depth): all zeros, every reason
+   FR_TP_NO_HISTORY.
+   Totals, every call: A_T = A + A', Q_T = Q + Q', n_T = (float)n + n', K_T = (float)K + K' (a
+   tiled accumulation's own counts); they become the view's history.
+   Picture: prep is fr_ctx_denoise's (with guide: fr_ctx_denoise_guided's) of (A_T, Q_T, n_T,
+   K_T - 1). A pixel with K_T < 2, a first frame without accepted history, has no variance and
+   takes var = (g g) / n_T, g = max((C_r + C_g) + C_b, FR_ERR_FLOOR), C the (demodulated) mean:
+   a relative standard error of 1, except that a miss (the sky is a function of the direction
+   alone) takes var = 0; valid iff |m_c| <= FR_DN_MEAN_MAX and var <= FR_DN_VAR_MAX (and
+   the guided feature caps). levels = 0: the mean (remodulated with a guide), its u8 and var
+   straight from prep; 1..6: that many levels of fr_ctx_denoise (guide: fr_ctx_denoise_guided).
+   The results land in fr_ctx_denoise's output buffers. One frame (K = 1) is accepted.
+   Enqueued behind the context's resolves; returns at once. guide NULL: unguided levels. opt
+   NULL: the FR_TP_*_DEFAULT values. FR_EARG, with nothing enqueued and no state moved: no live
+   accumulation, no Q, shard_count != 1, levels > 6, k or an option out of range, no G-buffer, a
+   G-buffer whose scene upload, camera, width or height differs from the live accumulation's. */
+#define FR_TP_NONE 0xFFFFFFFFu /* the source of a pixel without one */
+#define FR_TP_REUSED 0u
+#define FR_TP_NO_HISTORY 1u
+#define FR_TP_MISS 2u
+#define FR_TP_OFFSCREEN 3u /* behind the previous camera, or out of its frame */
+#define FR_TP_ID 4u
+#define FR_TP_NORMAL 5u
+#define FR_TP_PLANE 6u
+#define FR_TP_HISTORY 7u /* the source's totals are empty or not finite */
+#define FR_TP_N_MAX_DEFAULT 32.0f
+#define FR_TP_N_MAX_SPECULAR_DEFAULT 4.0f
+#define FR_TP_SIGMA_Z_DEFAULT 0.03125f /* 2^-5 */
+#define FR_TP_NORMAL_MIN_DEFAULT 0.9f
+#define FR_TP_N_MAX_MAX 16777216.0f /* 2^24 */
+typedef struct fr_temporal {
+  float n_max, n_max_specular; /* samples; n_max finite in (0, 2^24], n_max_specular finite in [0, 2^24] */
+  float sigma_z;               /* finite, in (0, 1024] */
+  float normal_min;            /* finite, in [-1, 1] */
+  uint32_t pad[4];             /* 0 */
+} fr_temporal;                 /* 32 bytes */
+int fr_ctx_temporal(fr_ctx* ctx, uint32_t levels, float k, const fr_denoise_guide* guide, const fr_temporal* opt);
+/* Drops the history (host state only): the next fr_ctx_temporal starts with an empty prior. */
+int fr_ctx_temporal_reset(fr_ctx* ctx);
+/* Waits for the last fr_ctx_temporal; any pointer may be NULL. prior_a, prior_q, total_a, total_q
+   W*H*3 f32; prior_n, prior_k, total_n, total_k W*H f32; source (y0 W + x0, or FR_TP_NONE) and
+   reason (FR_TP_*) W*H, row-major. FR_EARG if no fr_ctx_temporal was enqueued since the buffers
+   were (re)allocated. */
+int fr_ctx_download_temporal(fr_ctx* ctx, float* prior_a, float* prior_q, float* prior_n, float* prior_k,
+                             float* total_a, float* total_q, float* total_n, float* total_k, uint32_t* source,
+                             uint32_t* reason);
 
 /* ---- persistent multi-device context (tracer.rs:83-134 render_mt, one device per shard) ----
    Entry i of `devices` renders row shard i of n of every frame on its own fr_ctx (device
