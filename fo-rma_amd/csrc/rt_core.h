@@ -97,9 +97,14 @@ FR_HD Rng rng_seed(uint64_t seed, uint32_t pixel, uint32_t block) {
 FR_HD uint32_t rotl32(uint32_t x, int k) { return (x << k) | (x >> (32 - k)); }
 
 FR_HD uint32_t rng_next(Rng& r) {  // xoshiro128+ 1.0
-  const uint32_t result = r.s0 + r.s3;
+  uint32_t result = r.s0 + r.s3;
   const uint32_t t = r.s1 << 9;
 #if defined(__HIP_DEVICE_COMPILE__)
+  // The draw is formed before the state moves on: it and the two words it read pass through one
+  // empty asm, so the transition below cannot be scheduled ahead of the sum. Left free, the
+  // compiler formed s0' and s3' early into fresh registers, kept the old words for a late sum,
+  // and copied the new ones back at the next join (two v_mov_b32 per try of the lane loop).
+  asm("" : "+v"(result), "+v"(r.s0), "+v"(r.s3));
   // the same state transition with gfx950's three-input v_bitop3_b32 (0x96 = a ^ b ^ c):
   // s2' = s2 ^ s0 ^ t, s1' = s1 ^ (s2 ^ s0), s0' = s0 ^ (s3 ^ s1), s3' = rotl(s3 ^ s1, 11);
   // 6 VALU per draw instead of 7 (LLVM does not form bitop3 from xor chains); C3 trace
@@ -488,6 +493,48 @@ FR_HD bool recip_box_ok(float x) {
   const float ax = __builtin_fabsf(x);
   return (ax >= 0x1p-100f) & (ax < 0x1p126f);
 }
+// The same guard for a segment's three components at once, conservative: ok only if
+//   min3(|x|, |y|, |z|) >= 2^-100  and  (|x| + |y|) + |z| < 2^126
+// (one v_min3_f32 and two adds with |.| source modifiers, two compares and one mask AND, for the
+// six compares and five ANDs of three recip_box_ok).
+//   - ok here => recip_box_ok of every component. A sum of non-negative terms rounds to no less
+//     than its largest term (RN is monotonic), so a sum under 2^126 has every component under it;
+//     a sum that overflows is +inf and fails. An infinite component makes the sum +inf; a NaN
+//     component, which the NaN-ignoring min3 may skip, makes the sum NaN, and NaN < 2^126 is false.
+//     That matters: the fallback turns a NaN reciprocal into -2^100 (box_inv_clamp's maxNum /
+//     minNum), which recip_nr would not.
+//   - It may refuse a segment whose components each pass (a sum at or over 2^126 of components
+//     under it): that lane takes the IEEE division and the clamp, which equal the fast path
+//     wherever both are valid: recip_nr is RN(1 / x) on its range, and |RN(1 / x)| <= 2^100 for
+//     |x| >= 2^-100, where the clamp is the identity.
+// (tests/c/guard_root_check.cpp goes through the triples at the thresholds; fr_selftest_boxinv
+// returns the device's reciprocals for them.)
+FR_HD float fmin3_abs(float a, float b, float c) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  float r;
+  asm("v_min3_f32 %0, |%1|, |%2|, |%3|" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+  return r;
+#else
+  return fminf(fminf(fabsf(a), fabsf(b)), fabsf(c));
+#endif
+}
+FR_HD bool recip_box_ok3(V3 d) {
+  const float sum = (__builtin_fabsf(d.x) + __builtin_fabsf(d.y)) + __builtin_fabsf(d.z);
+  return (fmin3_abs(d.x, d.y, d.z) >= 0x1p-100f) & (sum < 0x1p126f);
+}
+#if defined(__HIP__)
+// A segment's box reciprocals, RN(1 / d) clamped to +-2^100 per component: recip_nr under the
+// guard, the IEEE division and the clamp on the lanes it refuses (a real branch, skipped by
+// waves without such a lane)
+__device__ __forceinline__ V3 seg_box_inv(V3 d) {
+  V3 inv{recip_nr(d.x), recip_nr(d.y), recip_nr(d.z)};
+  if (!recip_box_ok3(d)) {
+    inv = V3{1.0f / d.x, 1.0f / d.y, 1.0f / d.z};
+    inv = V3{box_inv_clamp(inv.x), box_inv_clamp(inv.y), box_inv_clamp(inv.z)};
+  }
+  return inv;
+}
+#endif
 FR_HD Slab slab3_box(V3 lo, V3 hi, V3 o, V3 inv, V3 oinv) {
   (void)o;  // (slab3's signature; o enters through oinv)
   return slab3_fused(lo, hi, oinv, inv);

@@ -23,6 +23,17 @@ __global__ void camray_kernel(KCam cm, const float* in, uint32_t n, uint32_t* ou
   for (int k = 0; k < 12; ++k) out[12 * i + k] = __float_as_uint(w[k]);
 }
 
+// The trace kernel's segment set-up (rt_core.h seg_box_inv) on direction i: its three box
+// reciprocals' bits
+__global__ void boxinv_kernel(const float* in, uint32_t n, uint32_t* out) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const V3 inv = seg_box_inv(V3{in[3 * i], in[3 * i + 1], in[3 * i + 2]});
+  out[3 * i] = __float_as_uint(inv.x);
+  out[3 * i + 1] = __float_as_uint(inv.y);
+  out[3 * i + 2] = __float_as_uint(inv.z);
+}
+
 __global__ void ops_kernel(int op, const float* a, const float* b, uint32_t n, float* out) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -179,6 +190,22 @@ int fr_selftest_camray(int device, const fr_camera* cam, const float* in, uint32
   if (n) hipLaunchKernelGGL(camray_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, kc, din, n, dout);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpy(out, dout, n * 12 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  HIPCHK(hipFree(din));
+  HIPCHK(hipFree(dout));
+  return FR_OK;
+}
+
+int fr_selftest_boxinv(int device, const float* in, uint32_t n, uint32_t* out) {
+  if (!in || !out) return set_error(FR_EARG, "fr_selftest_boxinv: null argument");
+  SET_DEVICE(device);
+  float* din = nullptr;
+  uint32_t* dout = nullptr;
+  HIPCHK(hipMalloc(&din, (n ? n : 1) * 3 * sizeof(float)));
+  HIPCHK(hipMalloc(&dout, (n ? n : 1) * 3 * sizeof(uint32_t)));
+  HIPCHK(hipMemcpy(din, in, n * 3 * sizeof(float), hipMemcpyHostToDevice));
+  if (n) hipLaunchKernelGGL(boxinv_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, din, n, dout);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpy(out, dout, n * 3 * sizeof(uint32_t), hipMemcpyDeviceToHost));
   HIPCHK(hipFree(din));
   HIPCHK(hipFree(dout));
   return FR_OK;

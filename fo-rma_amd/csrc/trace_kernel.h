@@ -282,6 +282,18 @@ __device__ __forceinline__ uint32_t lanes_in(unsigned long long m) {
   return static_cast<uint32_t>(__builtin_popcount(static_cast<uint32_t>(m)) +
                                __builtin_popcount(static_cast<uint32_t>(m >> 32)));
 }
+// The same count as one 64-bit scalar popcount with a 32-bit result: the count passes through an
+// empty asm as a 32-bit scalar, so the compiler cannot widen the compare that follows to the
+// 64-bit one it moves to the VALU. Not for a loop's own test: the asm (convergent, like every
+// device asm) keeps the loop from being rotated, and the rejection loop then carries its state
+// through 14 register copies per pass.
+__device__ __forceinline__ uint32_t lanes_in_once(unsigned long long m) {
+  uint32_t c = static_cast<uint32_t>(__builtin_popcountll(m));
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm("" : "+s"(c));
+#endif
+  return c;
+}
 __device__ __forceinline__ uint32_t lanes_set(bool b) { return lanes_in(__builtin_amdgcn_ballot_w64(b)); }
 
 // LDS byte address of a pointer into __shared__ memory, and the u32 at such an address
@@ -650,7 +662,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(FR_NUM_SGPR)
     // runs for several lanes at once instead of in nearly every iteration for one or two.
     // Only when work starts changes, never what a sample computes (results bit-identical).
     constexpr uint32_t CLAIM_MIN = NIB ? (BVH ? FR_CLAIM_MIN_BVH : FR_CLAIM_MIN_NIB) : FR_CLAIM_MIN;
-    if (m && (CLAIM_MIN <= 1 || lanes_in(m) >= CLAIM_MIN || m == __ballot(1))) {
+    if (m && (CLAIM_MIN <= 1 || lanes_in_once(m) >= CLAIM_MIN || m == __ballot(1))) {
       SEC(SC_CLAIM);
       // 0. claim work items: the free lanes take consecutive items of the wave's batch;
       // when it runs out, the first free lane reserves the next batch of kBatch = 64
@@ -832,7 +844,15 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(FR_NUM_SGPR)
     PROF_MARK(PF_CLAIM);
     bool ended = false;
     V3 term{0.0f, 0.0f, 0.0f};
-    uint32_t tsky = kDeferAbsorbed;  // DEFER: the terminal as sky parameter bits
+    // DEFER: the terminal as sky parameter bits. Every place that ends a path writes it (the sky
+    // its parameter, a hit or an absorbed scatter kDeferAbsorbed), so it has no value before:
+    // a default assigned here was a v_mov_b32 in every iteration, for every lane
+    uint32_t tsky;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "=v"(tsky));  // (defined, by no instruction)
+#else
+    tsky = kDeferAbsorbed;
+#endif
     if (need != NEED_NONE) {
       SEC(SC_NEED);
       // 1. merged rejection loop
@@ -889,57 +909,73 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(FR_NUM_SGPR)
         mrej = __builtin_amdgcn_ballot_w64(dd >= kUnitBallScaled);
       }
       SEC(SC_ACC);
-      if (!lane_in(mrej)) {
-        // the accepted point is k 2^-23 per coordinate (2r - 1, exact), k = (px, py, pz):
-        // the scale is folded into the operation that uses it (below)
-        if (!lane_in(msph)) {
-          SEC(SC_CAM);
-          // Camera::get_ray (camera.rs:62-72)
-          // scalar loads of the camera from the kernarg segment, here, rather than 19
-          // SGPRs held (and spilled) across the loop
-          // An axial camera (every bundled scene's) takes the short form: one scalar branch on
-          // the host's verdict, a run-time fact of the frame (update() moves the camera)
-          KCam cm = kernarg_reload(args, [](const auto& a) { return a.cam; });
+      // The accepted lanes: camera lanes, then scatter lanes, as two branches in sequence on
+      // disjoint lane masks, not an if / else. Each writes o and d where they live: in the
+      // linear order the two sides of an if / else run in, the camera side's new direction and
+      // the scatter side's old one are live together, so the new direction went to fresh
+      // registers and was copied into d's where the sides joined (two v_mov_b32 per iteration,
+      // and the moves that shuffled `need` there).
+      // the accepted point is k 2^-23 per coordinate (2r - 1, exact), k = (px, py, pz):
+      // the scale is folded into the operation that uses it (below)
+      const unsigned long long macc = ~mrej;
+      if (lane_in(macc & ~msph)) {
+        SEC(SC_CAM);
+        // Camera::get_ray (camera.rs:62-72)
+        // scalar loads of the camera from the kernarg segment, here, rather than 19
+        // SGPRs held (and spilled) across the loop
+        // An axial camera (every bundled scene's) takes the short form: one scalar branch on
+        // the host's verdict, a run-time fact of the frame (update() moves the camera)
+        KCam cm = kernarg_reload(args, [](const auto& a) { return a.cam; });
 #if defined(__HIP_DEVICE_COMPILE__)
-          // (dz loaded with the rest, ahead of the branch: left to the axial side alone it
-          // became a second scalar load, and a second wait, inside it)
-          asm volatile("" : "+s"(cm.dz));
+        // (dz loaded with the rest, ahead of the branch: left to the axial side alone it
+        // became a second scalar load, and a second wait, inside it)
+        asm volatile("" : "+s"(cm.dz));
 #endif
-          const CamLens rd = cam_lens(cm, px, py);
-          CamRay cr;
-          if (cm.lens_pre & kCamAxial)
-            cr = cam_ray_axial(cm, rd, d.x, d.y);
-          else
-            cr = cam_ray(cm, rd, d.x, d.y);
+        const CamLens rd = cam_lens(cm, px, py);
+        // (two branches in sequence here too, for the same reason; the second form's flag
+        // through an empty asm, or the compiler threads the two back into an if / else)
+        uint32_t general = (cm.lens_pre & kCamAxial) ^ kCamAxial;
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm volatile("" : "+s"(general));
+#endif
+        if (cm.lens_pre & kCamAxial) {
+          const CamRay cr = cam_ray_axial(cm, rd, d.x, d.y);
           o = cr.o;
           d = cr.d;
-          if (!NIB) depth = 0;
+        }
+        if (general) {
+          const CamRay cr = cam_ray(cm, rd, d.x, d.y);
+          o = cr.o;
+          d = cr.d;
+        }
+        if (!NIB) depth = 0;
+        have_ray = true;
+      }
+      if (lane_in(macc & msph)) {
+        SEC(SC_SCAT);
+        bool ok = true;
+        V3 dir;
+        if (!DIFFUSE && smetal) {
+          const V3 r{px * kSignedUnitScale, py * kSignedUnitScale, pz * kSignedUnitScale};
+          dir = add(d, scl(sfuzz, r));  // reflected + fuzz * rus
+          ok = dot(dir, sn) > 0.0f;     // sphere.rs:104 / plane.rs:121
+        } else {
+          // ((p + n) + rus) - p; p + n + k 2^-23 as one fma (the product is exact)
+          const V3 dr{__builtin_fmaf(px, kSignedUnitScale, d.x), __builtin_fmaf(py, kSignedUnitScale, d.y),
+                      __builtin_fmaf(pz, kSignedUnitScale, d.z)};
+          dir = sub(dr, o);
+        }
+        if (ok) {
+          if (!(NIB && DIFFUSE)) push(sbest);  // (NIB && DIFFUSE kernels pushed at the shading step)
+          if (!NIB) ++depth;
+          d = dir;
           have_ray = true;
         } else {
-          SEC(SC_SCAT);
-          bool ok = true;
-          V3 dir;
-          if (!DIFFUSE && smetal) {
-            const V3 r{px * kSignedUnitScale, py * kSignedUnitScale, pz * kSignedUnitScale};
-            dir = add(d, scl(sfuzz, r));  // reflected + fuzz * rus
-            ok = dot(dir, sn) > 0.0f;     // sphere.rs:104 / plane.rs:121
-          } else {
-            // ((p + n) + rus) - p; p + n + k 2^-23 as one fma (the product is exact)
-            const V3 dr{__builtin_fmaf(px, kSignedUnitScale, d.x), __builtin_fmaf(py, kSignedUnitScale, d.y),
-                        __builtin_fmaf(pz, kSignedUnitScale, d.z)};
-            dir = sub(dr, o);
-          }
-          if (ok) {
-            if (!(NIB && DIFFUSE)) push(sbest);  // (NIB && DIFFUSE kernels pushed at the shading step)
-            if (!NIB) ++depth;
-            d = dir;
-            have_ray = true;
-          } else {
-            ended = true;  // absorbed: get_color returns 0
-          }
+          ended = true;  // absorbed: get_color returns 0
+          tsky = kDeferAbsorbed;
         }
-        need = NEED_NONE;
       }
+      if (lane_in(macc)) need = NEED_NONE;
     }
     PROF_MARK(PF_REJ);
     if (have_ray) {
@@ -947,17 +983,11 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(FR_NUM_SGPR)
       // 2. closest hit over the list in order (tracer.rs:190-200): only the accepted t
       // of each test is needed here; the record is formed for the winner below.
       ++nseg;
-      V3 inv{recip_nr(d.x), recip_nr(d.y), recip_nr(d.z)};
-      // (non-short-circuit: one branch to the rare fallback instead of three nested ones)
-      // the box test's reciprocal is RN(1 / d) clamped to +-2^100 (rt_core.h box_inv):
-      // recip_nr's range is narrowed to |d| >= 2^-100, where the clamp is the identity, and
-      // the fallback clamps
-      const int rok = static_cast<int>(recip_box_ok(d.x)) & static_cast<int>(recip_box_ok(d.y)) &
-                      static_cast<int>(recip_box_ok(d.z));
-      if (!rok) {
-        inv = V3{1.0f / d.x, 1.0f / d.y, 1.0f / d.z};
-        inv = V3{box_inv_clamp(inv.x), box_inv_clamp(inv.y), box_inv_clamp(inv.z)};
-      }
+      // the box test's reciprocal is RN(1 / d) clamped to +-2^100 (rt_core.h seg_box_inv):
+      // recip_nr where one guard over the three components (recip_box_ok3) admits it, which
+      // implies |d_k| in [2^-100, 2^126) for each, where the clamp is the identity; the rare
+      // fallback divides and clamps (one branch)
+      const V3 inv = seg_box_inv(d);
       const V3 boinv{o.x * inv.x, o.y * inv.y, o.z * inv.z};  // (box tests only)
       const float a_dd = dot(d, d);
       const SphereSeg ssg = sphere_seg(a_dd);  // unused (removed) in kernels without spheres
@@ -1021,7 +1051,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(FR_NUM_SGPR)
           // inf - inf = NaN, which culled boxes the ray is inside. With the clamp, o inv is
           // finite and a slab that holds the ray's hit by the padding (>= 1e-4) stays
           // >= 1e-4 * 2^100 wide on that axis. (Today `inv` arrives clamped: a lane with
-          // recip_box_ok has |inv| <= 2^100 and a wave without one clamps every lane above, so
+          // recip_box_ok3 has |inv| <= 2^100 and a wave without one clamps every lane above, so
           // the fmed3 changes no value; it keeps the cull right if that fallback ever changes.)
           const V3 invc{__builtin_amdgcn_fmed3f(inv.x, -kBvhInvClamp, kBvhInvClamp),
                         __builtin_amdgcn_fmed3f(inv.y, -kBvhInvClamp, kBvhInvClamp),
@@ -1308,6 +1338,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(FR_NUM_SGPR)
         DIAG_WAVE(DG_HIT_W);
         ++nhit;
         ended = true;  // unless a scatter continues the path
+        tsky = kDeferAbsorbed;
         have_ray = false;
         if (NIB ? (dmask != 0u && (wnib & dmask) == dmask) : depth < kp.max_depth) {
           SEC(SC_SHADE);

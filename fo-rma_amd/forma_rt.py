@@ -144,7 +144,7 @@ EXPORTS = (
     "fr_ctx_adapt", "fr_ctx_download_counts", "fr_mctx_adapt",
     "fr_ctx_denoise", "fr_ctx_download_denoised", "fr_ctx_denoised_buffers",
     "fr_ctx_gbuffer", "fr_ctx_download_gbuffer", "fr_ctx_denoise_guided",
-    "fr_camera_axial", "fr_ctx_camera_path", "fr_selftest_camray",
+    "fr_camera_axial", "fr_ctx_camera_path", "fr_selftest_camray", "fr_selftest_boxinv",
     "fr_ctx_temporal", "fr_ctx_temporal_reset", "fr_ctx_download_temporal",
 )
 
@@ -259,6 +259,8 @@ def lib():
         L.fr_camera_axial.argtypes = [P(FrCamera)]
         L.fr_ctx_camera_path.argtypes = [vp, P(C.c_int)]
         L.fr_selftest_camray.argtypes = [C.c_int, P(FrCamera), f3, C.c_uint32, P(C.c_uint32)]
+    if hasattr(L, "fr_selftest_boxinv"):
+        L.fr_selftest_boxinv.argtypes = [C.c_int, f3, C.c_uint32, P(C.c_uint32)]
     if hasattr(L, "fr_ctx_gbuffer"):
         L.fr_ctx_gbuffer.argtypes = [vp, vp, P(FrCamera), C.c_uint32, C.c_uint32]
         L.fr_ctx_download_gbuffer.argtypes = [vp, P(C.c_uint32), f3, f3, f3, f3]

@@ -64,7 +64,7 @@ extern "C" {
                                fr_mctx_adapt; fr_ctx_denoise, fr_ctx_download_denoised,
                                fr_ctx_denoised_buffers; fr_ctx_gbuffer, fr_ctx_download_gbuffer,
                                fr_denoise_guide, fr_ctx_denoise_guided; fr_camera_axial,
-                               fr_ctx_camera_path, fr_selftest_camray; fr_temporal,
+                               fr_ctx_camera_path, fr_selftest_camray, fr_selftest_boxinv; fr_temporal,
                                fr_ctx_temporal, fr_ctx_temporal_reset, fr_ctx_download_temporal) */
 
 /* error codes */
@@ -339,6 +339,9 @@ int fr_ctx_camera_path(fr_ctx* ctx, int* axial);
    kx, ky the lens point's integers (2^23-scaled); out[12 i] = the general form's o.xyz, d.xyz,
    then the short form's, as bit patterns. FR_EARG when cam is not of the axial class. */
 int fr_selftest_camray(int device, const fr_camera* cam, const float* in, uint32_t n, uint32_t* out);
+/* Diagnostic: the trace kernel's segment set-up on the device for n directions in[3 i] = d.xyz;
+   out[3 i] = the bit patterns of the three box reciprocals, RN(1 / d) clamped to +-2^100. */
+int fr_selftest_boxinv(int device, const float* in, uint32_t n, uint32_t* out);
 /* FR_FLAG_ACCUMULATE: the next accumulating frame starts a new accumulation. */
 int fr_ctx_accum_reset(fr_ctx* ctx);
 /* Frames and samples per pixel in the accumulator (0, 0 when there is none). Host-side, as of
