@@ -2,9 +2,9 @@
 // one thread per pixel casts the pinhole primary ray through the scene's list, in list order,
 // and writes the winner's normal, root, point, index and attenuation as three 16-byte stores.
 // The arithmetic is gbuffer.h's. The primitive index is wave-uniform, so every record arrives
-// by scalar loads as in the trace kernel's list loop (rec_at); BVH scenes walk the list too:
-// the pass runs once per view, and the list makes list-order ties exact by construction.
-// No atomics, no scratch, no LDS.
+// by scalar loads as in the trace kernel's list loop (rec_at). Scenes that have a tree take
+// gbuffer_tree_kernel (cast.hip) from a camera within the tree's reach; this
+// kernel is the pass for every other scene and camera. No atomics, no scratch, no LDS.
 #include "gbuffer.h"
 
 #include <type_traits>

@@ -30,6 +30,7 @@
 #include "accum_error.h"
 #include "denoise.h"
 #include "gbuffer.h"
+#include "cast.h"
 #include "hipchk.h"
 #include "jit.h"
 #include "pack.h"
@@ -219,6 +220,22 @@ struct fr_ctx {
   uint64_t gb_uid = 0;
   fr_camera gb_cam{};
   bool gb_valid = false;
+  bool gb_tree = false;  // the last fr_ctx_gbuffer walked the scene's tree (fr_ctx_gbuffer_info)
+  // fr_ctx_cast: the rays' device copy (host rays arrive through the pinned
+  // h_cast_rays; ev_cast: the end of the last copy out of it), the hits as the G-buffer's three
+  // words per ray and the striped wave counter (cast.h), allocated on first use and replaced when n
+  // outgrows cast_cap rays. cast_valid: a cast was enqueued since they were (re)allocated.
+  float4* d_cast_rays = nullptr;
+  float4* h_cast_rays = nullptr;
+  size_t cap_cast_rays = 0, cap_cast_host = 0;  // bytes
+  hipEvent_t ev_cast = nullptr;
+  bool cast_copy_pending = false;
+  float4* d_hit0 = nullptr;
+  float4* d_hit1 = nullptr;
+  float4* d_hit_alb = nullptr;
+  uint32_t* d_cast_waves = nullptr;
+  uint32_t cast_cap = 0, cast_n = 0;
+  bool cast_valid = false, cast_tree = false;
   // fr_ctx_temporal. accum_gen: the accumulation generation, advanced whenever
   // accum_step starts a new accumulation. d_gb_cls: the G-buffer's scene's effective scatter
   // classes, gb_n of them, copied with every fr_ctx_gbuffer (the scene's own table dies with an
@@ -273,8 +290,9 @@ struct fr_ctx {
   // log 0: trace launches (on the launch's stream); log 1: whole renders (ev0 .. ev1)
   bool log_on = false;
   // log 2: the three stages of every fr_ctx_temporal call (prior, totals and prep, picture), on the sum stream
-  std::vector<hipEvent_t> log_ev[3];  // 2 per entry (start, end); reused across logs
-  size_t log_n[3] = {0, 0, 0};        // entries logged
+  // log 3: every cast kernel and G-buffer pass, on the sum stream
+  std::vector<hipEvent_t> log_ev[4];  // 2 per entry (start, end); reused across logs
+  size_t log_n[4] = {0, 0, 0, 0};     // entries logged
 };
 
 static hipError_t log_event(fr_ctx* c, int which, size_t k, hipStream_t st) {
@@ -618,13 +636,16 @@ void fr_ctx_free(fr_ctx* c) {
                   static_cast<void*>(c->d_tp_ta[1]), static_cast<void*>(c->d_tp_tq[0]),
                   static_cast<void*>(c->d_tp_tq[1]), static_cast<void*>(c->d_tp_g0), static_cast<void*>(c->d_tp_g1),
                   static_cast<void*>(c->d_tp_pa), static_cast<void*>(c->d_tp_pq), static_cast<void*>(c->d_tp_src),
-                  static_cast<void*>(c->d_tp_why)})
+                  static_cast<void*>(c->d_tp_why), static_cast<void*>(c->d_cast_rays), static_cast<void*>(c->d_hit0),
+                  static_cast<void*>(c->d_hit1), static_cast<void*>(c->d_hit_alb), static_cast<void*>(c->d_cast_waves)})
     if (d) (void)hipFree(d);
-  for (hipEvent_t e : {c->ev0, c->ev1, c->ev_start, c->ev_copy})
+  if (c->h_cast_rays) (void)hipHostFree(c->h_cast_rays);
+  for (hipEvent_t e : {c->ev0, c->ev1, c->ev_start, c->ev_copy, c->ev_cast})
     if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->ev_fslot)
     if (e) (void)hipEventDestroy(e);
-  for (const std::vector<hipEvent_t>* v : {&c->ev_trace, &c->ev_sum, &c->log_ev[0], &c->log_ev[1], &c->log_ev[2]})
+  for (const std::vector<hipEvent_t>* v : {&c->ev_trace, &c->ev_sum, &c->log_ev[0], &c->log_ev[1], &c->log_ev[2],
+                                             &c->log_ev[3]})
     for (hipEvent_t e : *v) (void)hipEventDestroy(e);
   for (hipStream_t s : {c->stream2, c->stream_sum, c->stream_copy})
     if (s) (void)hipStreamDestroy(s);
@@ -1267,6 +1288,32 @@ int fr_ctx_denoise(fr_ctx* c, uint32_t levels, float k) {
   return FR_OK;
 }
 
+// fr_ctx_gbuffer's default walk for a scene with a tree, by the rule of DESIGN.md §5: the tree,
+// because at 1080p on 10,000 spheres no pixel differed from the list pass and the tree pass's
+// median was below the list pass's minimum (profiles/gbuffer_tree_1080p.json).
+constexpr bool kGbTreeDefault = true;
+
+// The tables of a scene's device copy as the cast and G-buffer walks read them (cast.h).
+static CastScene cast_scene(const DeviceCopy* dc) {
+  const PackedScene& ps = dc->ps;
+  const char* b = static_cast<const char*>(dc->blob);
+  CastScene cs;
+  cs.gb.rec = reinterpret_cast<const float4*>(b + ps.off_rec);
+  cs.gb.runs = reinterpret_cast<const uint4*>(b + ps.off_runs);
+  cs.gb.cls = reinterpret_cast<const uint32_t*>(b + ps.off_cls);
+  cs.gb.att = reinterpret_cast<const float4*>(b + ps.off_att);
+  cs.gb.n_runs = ps.n_runs;
+  cs.gb.n = ps.facts.n;
+  cs.bvh = reinterpret_cast<const float4*>(b + ps.off_bvh);
+  cs.bvh_order = reinterpret_cast<const uint32_t*>(b + ps.off_bvh_order);
+  cs.lrec = reinterpret_cast<const float4*>(b + ps.off_lrec);
+  cs.segs = reinterpret_cast<const uint4*>(b + ps.off_segs);
+  cs.n_segs = ps.facts.bvh_ok ? ps.facts.n_segs : 0u;
+  cs.levels = ps.facts.bvh_levels;
+  cs.reach = bvh_origin_reach(ps.facts.bvh_extent, ps.facts.bvh_sphere_rmin);
+  return cs;
+}
+
 // The view's feature buffers: one pass on the sum stream, behind whatever is
 // enqueued there; nothing is waited for. Frames, A, Q, d_mean, d_u8, the pending render and its
 // stats are untouched: the pass reads the scene's device copy and writes buffers of its own.
@@ -1293,14 +1340,15 @@ int fr_ctx_gbuffer(fr_ctx* c, fr_scene* scene, const fr_camera* cam, uint32_t wi
     c->gb_h = height;
   }
   const PackedScene& ps = dc->ps;
-  const char* b = static_cast<const char*>(dc->blob);
-  GbScene gs;
-  gs.rec = reinterpret_cast<const float4*>(b + ps.off_rec);
-  gs.runs = reinterpret_cast<const uint4*>(b + ps.off_runs);
-  gs.cls = reinterpret_cast<const uint32_t*>(b + ps.off_cls);
-  gs.att = reinterpret_cast<const float4*>(b + ps.off_att);
-  gs.n_runs = ps.n_runs;
-  gs.n = ps.facts.n;
+  const CastScene cs = cast_scene(dc);
+  const GbScene& gs = cs.gb;
+  // scenes with a tree walk it (gbuffer_tree_kernel) from a camera within the
+  // scene's reach (plan.cpp's cam_near). FR_BVH=0 keeps the list; FR_GBUFFER_WALK=list / tree
+  // picks the walk whatever the default is (A/B: tools/gbuffer_time.py sets it for itself)
+  const char* walk = getenv("FR_GBUFFER_WALK");
+  const bool want_tree = walk && !strcmp(walk, "tree") ? true : walk && !strcmp(walk, "list") ? false : kGbTreeDefault;
+  const bool tree = want_tree && cs.n_segs > 0 && !env.bvh_off &&
+                    camera_reach(*cam) <= bvh_origin_reach(ps.facts.bvh_extent, ps.facts.bvh_sphere_rmin);
   const GbCam gc{V3{cam->position[0], cam->position[1], cam->position[2]},
                  V3{cam->lower_left[0], cam->lower_left[1], cam->lower_left[2]},
                  V3{cam->horizontal[0], cam->horizontal[1], cam->horizontal[2]},
@@ -1313,7 +1361,13 @@ int fr_ctx_gbuffer(fr_ctx* c, fr_scene* scene, const fr_camera* cam, uint32_t wi
     c->gb_valid = false;
     if ((rc = grow(c->d_gb_cls, c->cap_gb_cls, cls_bytes))) return rc;
   }
-  HIPCHK(launch_gbuffer(c->stream_sum, gs, gc, width, height, c->d_gb0, c->d_gb1, c->d_gb_alb));
+  if (c->log_on) HIPCHK(log_start(c, 3, c->stream_sum));
+  if (tree)
+    HIPCHK(launch_gbuffer_tree(c->stream_sum, cs, gc, width, height, c->d_gb0, c->d_gb1, c->d_gb_alb));
+  else
+    HIPCHK(launch_gbuffer(c->stream_sum, gs, gc, width, height, c->d_gb0, c->d_gb1, c->d_gb_alb));
+  if (c->log_on) HIPCHK(log_end(c, 3, c->stream_sum));
+  c->gb_tree = tree;
   if (cls_bytes) HIPCHK(hipMemcpyAsync(c->d_gb_cls, gs.cls, cls_bytes, hipMemcpyDeviceToDevice, c->stream_sum));
   c->gb_n = gs.n;
   c->gb_uid = dc->uid;
@@ -1322,18 +1376,16 @@ int fr_ctx_gbuffer(fr_ctx* c, fr_scene* scene, const fr_camera* cam, uint32_t wi
   return FR_OK;
 }
 
-int fr_ctx_download_gbuffer(fr_ctx* c, uint32_t* prim, float* depth, float* normal, float* position, float* albedo) {
-  if (!c) return set_error(FR_EARG, "fr_ctx_download_gbuffer: null ctx");
-  if (!c->gb_valid) return set_error(FR_EARG, "fr_ctx_download_gbuffer: no G-buffer (fr_ctx_gbuffer first)");
-  SET_DEVICE(c->device);
-  const size_t px = static_cast<size_t>(c->gb_w) * c->gb_h;
-  // the device words are unpacked on the host: only the planes asked for are copied
+// px pixels (or hits) of the three device words, unpacked on the host after a wait for the sum
+// stream: only the planes asked for are copied.
+static int download_words(fr_ctx* c, size_t px, const float4* d0, const float4* d1, const float4* dalb, uint32_t* prim,
+                          float* depth, float* normal, float* position, float* albedo) {
   const bool want0 = depth || normal, want1 = prim || position;
   std::vector<float> g0(want0 ? 4 * px : 0), g1(want1 ? 4 * px : 0), al(albedo ? 4 * px : 0);
   hipStream_t st = c->stream_sum;
-  if (want0) HIPCHK(hipMemcpyAsync(g0.data(), c->d_gb0, px * sizeof(float4), hipMemcpyDeviceToHost, st));
-  if (want1) HIPCHK(hipMemcpyAsync(g1.data(), c->d_gb1, px * sizeof(float4), hipMemcpyDeviceToHost, st));
-  if (albedo) HIPCHK(hipMemcpyAsync(al.data(), c->d_gb_alb, px * sizeof(float4), hipMemcpyDeviceToHost, st));
+  if (want0) HIPCHK(hipMemcpyAsync(g0.data(), d0, px * sizeof(float4), hipMemcpyDeviceToHost, st));
+  if (want1) HIPCHK(hipMemcpyAsync(g1.data(), d1, px * sizeof(float4), hipMemcpyDeviceToHost, st));
+  if (albedo) HIPCHK(hipMemcpyAsync(al.data(), dalb, px * sizeof(float4), hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   for (size_t i = 0; i < px; ++i) {
     if (prim) memcpy(&prim[i], &g1[4 * i + 3], 4);
@@ -1342,6 +1394,109 @@ int fr_ctx_download_gbuffer(fr_ctx* c, uint32_t* prim, float* depth, float* norm
     if (position) memcpy(&position[3 * i], &g1[4 * i], 12);
     if (albedo) memcpy(&albedo[3 * i], &al[4 * i], 12);
   }
+  return FR_OK;
+}
+
+int fr_ctx_download_gbuffer(fr_ctx* c, uint32_t* prim, float* depth, float* normal, float* position, float* albedo) {
+  if (!c) return set_error(FR_EARG, "fr_ctx_download_gbuffer: null ctx");
+  if (!c->gb_valid) return set_error(FR_EARG, "fr_ctx_download_gbuffer: no G-buffer (fr_ctx_gbuffer first)");
+  SET_DEVICE(c->device);
+  return download_words(c, static_cast<size_t>(c->gb_w) * c->gb_h, c->d_gb0, c->d_gb1, c->d_gb_alb, prim, depth, normal,
+                        position, albedo);
+}
+
+int fr_ctx_gbuffer_info(fr_ctx* c, int* tree) {
+  if (!c || !tree) return set_error(FR_EARG, "fr_ctx_gbuffer_info: null argument");
+  if (!c->gb_valid) return set_error(FR_EARG, "fr_ctx_gbuffer_info: no G-buffer (fr_ctx_gbuffer first)");
+  *tree = c->gb_tree ? 1 : 0;
+  return FR_OK;
+}
+
+// Ray queries: one cast kernel on the sum stream, behind whatever is enqueued
+// there; nothing is waited for but the pinned staging buffer's previous copy. Frames, A, Q, the
+// outputs, the pending render and its stats, the G-buffer and the history are untouched.
+int fr_ctx_cast(fr_ctx* c, fr_scene* scene, const fr_ray* rays, uint32_t n, uint32_t flags) {
+  if (!c || !scene || !rays) return set_error(FR_EARG, "fr_ctx_cast: null argument");
+  if (!n || n > (1u << 27)) return set_error(FR_EARG, "fr_ctx_cast: n %u must be 1 to 2^27", n);
+  if (flags & ~(FR_CAST_LIST | FR_CAST_RAYS_DEVICE)) return set_error(FR_EARG, "fr_ctx_cast: unknown flags 0x%x", flags);
+  SET_DEVICE(c->device);
+  const PlanEnv env = read_plan_env();
+  DeviceCopy* dc = nullptr;
+  int rc;
+  if ((rc = upload_scene(scene, c->device, env.bvh_force, &dc))) return rc;
+  const size_t ray_bytes = static_cast<size_t>(n) * sizeof(fr_ray);
+  const bool host_rays = !(flags & FR_CAST_RAYS_DEVICE);
+  if (n > c->cast_cap || !c->d_cast_waves) {
+    HIPCHK(hipStreamSynchronize(c->stream_sum));  // the kernels and copies that use the old buffers
+    c->cast_valid = false;
+    c->cast_cap = 0;
+    const size_t bytes = static_cast<size_t>(n) * sizeof(float4);
+    size_t caps[3] = {};  // (grow with no capacity: each buffer is replaced)
+    if ((rc = grow(c->d_hit0, caps[0], bytes))) return rc;
+    if ((rc = grow(c->d_hit1, caps[1], bytes))) return rc;
+    if ((rc = grow(c->d_hit_alb, caps[2], bytes))) return rc;
+    if (!c->d_cast_waves) HIPCHK(hipMalloc(&c->d_cast_waves, kCastWaveBytes));
+    if (!c->ev_cast) HIPCHK(hipEventCreateWithFlags(&c->ev_cast, hipEventDisableTiming));
+    c->cast_cap = n;
+  }
+  const float4* d_rays = reinterpret_cast<const float4*>(rays);
+  if (host_rays) {
+    if (c->cap_cast_rays < ray_bytes) {
+      HIPCHK(hipStreamSynchronize(c->stream_sum));  // an earlier cast may still read the smaller copy
+      if ((rc = grow(c->d_cast_rays, c->cap_cast_rays, ray_bytes))) return rc;
+    }
+    // the caller's rays leave through a pinned buffer the context owns: copied before the
+    // call returns, and the device copy stays asynchronous
+    if (c->cast_copy_pending) HIPCHK(hipEventSynchronize(c->ev_cast));
+    c->cast_copy_pending = false;
+    if (c->cap_cast_host < ray_bytes) {
+      if (c->h_cast_rays) HIPCHK(hipHostFree(c->h_cast_rays));
+      c->h_cast_rays = nullptr;
+      c->cap_cast_host = 0;
+      HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&c->h_cast_rays), ray_bytes, hipHostMallocDefault));
+      c->cap_cast_host = ray_bytes;
+    }
+    memcpy(c->h_cast_rays, rays, ray_bytes);
+    HIPCHK(hipMemcpyAsync(c->d_cast_rays, c->h_cast_rays, ray_bytes, hipMemcpyHostToDevice, c->stream_sum));
+    HIPCHK(hipEventRecord(c->ev_cast, c->stream_sum));
+    c->cast_copy_pending = true;
+    d_rays = c->d_cast_rays;
+  }
+  const CastScene cs = cast_scene(dc);
+  const bool tree = cs.n_segs > 0 && !(flags & FR_CAST_LIST);
+  HIPCHK(hipMemsetAsync(c->d_cast_waves, 0, kCastWaveBytes, c->stream_sum));
+  if (c->log_on) HIPCHK(log_start(c, 3, c->stream_sum));
+  HIPCHK(launch_cast(c->stream_sum, cs, tree, d_rays, n, c->d_hit0, c->d_hit1, c->d_hit_alb, c->d_cast_waves));
+  if (c->log_on) HIPCHK(log_end(c, 3, c->stream_sum));
+  c->cast_n = n;
+  c->cast_tree = tree;
+  c->cast_valid = true;
+  return FR_OK;
+}
+
+int fr_ctx_download_hits(fr_ctx* c, uint32_t* prim, float* t, float* normal, float* position, float* albedo) {
+  if (!c) return set_error(FR_EARG, "fr_ctx_download_hits: null ctx");
+  if (!c->cast_valid) return set_error(FR_EARG, "fr_ctx_download_hits: no hits (fr_ctx_cast first)");
+  SET_DEVICE(c->device);
+  return download_words(c, c->cast_n, c->d_hit0, c->d_hit1, c->d_hit_alb, prim, t, normal, position, albedo);
+}
+
+int fr_ctx_cast_info(fr_ctx* c, fr_cast_info* out) {
+  if (!c || !out) return set_error(FR_EARG, "fr_ctx_cast_info: null argument");
+  if (!c->cast_valid) return set_error(FR_EARG, "fr_ctx_cast_info: no hits (fr_ctx_cast first)");
+  SET_DEVICE(c->device);
+  std::vector<uint32_t> stripes(kCastWaveBytes / 4);
+  HIPCHK(hipMemcpyAsync(stripes.data(), c->d_cast_waves, kCastWaveBytes, hipMemcpyDeviceToHost, c->stream_sum));
+  HIPCHK(hipStreamSynchronize(c->stream_sum));
+  uint32_t waves[2] = {0, 0};
+  for (uint32_t k = 0; k < kCastStripes; ++k) {
+    waves[0] += stripes[k * kCastStripeWords];
+    waves[1] += stripes[k * kCastStripeWords + 1];
+  }
+  out->n = c->cast_n;
+  out->tree = c->cast_tree ? 1u : 0u;
+  out->waves_tree = waves[0];
+  out->waves_list = waves[1];
   return FR_OK;
 }
 
@@ -1657,25 +1812,26 @@ int fr_ctx_trace_log(fr_ctx* c, int enable) {
     HIPCHK(hipStreamSynchronize(c->stream));
     HIPCHK(hipStreamSynchronize(c->stream2));
     HIPCHK(hipStreamSynchronize(c->stream_sum));
-    c->log_n[0] = c->log_n[1] = c->log_n[2] = 0;
+    c->log_n[0] = c->log_n[1] = c->log_n[2] = c->log_n[3] = 0;
   }
   c->log_on = enable != 0;
   return FR_OK;
 }
 
 int fr_ctx_trace_log_read(fr_ctx* c, int which, double* ms, uint32_t cap, uint32_t* n) {
-  if (!c || !n || which < 0 || which > 4) return set_error(FR_EARG, "fr_ctx_trace_log_read: bad argument");
+  if (!c || !n || which < 0 || which > 5) return set_error(FR_EARG, "fr_ctx_trace_log_read: bad argument");
   SET_DEVICE(c->device);
   HIPCHK(hipStreamSynchronize(c->stream));
   HIPCHK(hipStreamSynchronize(c->stream2));
   HIPCHK(hipStreamSynchronize(c->stream_sum));  // a pipelined render's end event is recorded there
   // which 0 / 1: durations of the trace launches / renders; 2 / 3: their start and end times
   // (two values each) from the first logged trace launch's start (a timeline); 4: durations of
-  // the stages of the fr_ctx_temporal calls, three entries per call
-  const int w = which == 4 ? 2 : which & 1;
+  // the stages of the fr_ctx_temporal calls, three entries per call; 5: durations of the cast
+  // kernels and G-buffer passes
+  const int w = which == 5 ? 3 : which == 4 ? 2 : which & 1;
   *n = static_cast<uint32_t>(c->log_n[w]);
   for (size_t i = 0; i < c->log_n[w] && ms; ++i) {
-    if (which < 2 || which == 4) {
+    if (which < 2 || which >= 4) {
       if (i >= cap) break;
       float t = 0.0f;
       HIPCHK(hipEventElapsedTime(&t, c->log_ev[w][2 * i], c->log_ev[w][2 * i + 1]));

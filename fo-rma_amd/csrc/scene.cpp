@@ -14,6 +14,7 @@
 
 #include "internal.h"
 #include "json_min.h"
+#include "gbuffer.h"
 #include "rt_core.h"
 
 namespace fr {
@@ -504,6 +505,18 @@ int fr_camera_translate(fr_camera* cam, const float delta[3]) {
 }
 
 // tracer.rs:30-50, key bits 00EQADWS
+int fr_camera_pixel_ray(const fr_camera* cam, uint32_t x, uint32_t y, uint32_t W, uint32_t H, fr_ray* out) {
+  if (!cam || !out || !W || !H || x >= W || y >= H) return set_error(FR_EARG, "fr_camera_pixel_ray: bad arguments");
+  using fr::V3;
+  const fr::GbCam gc{V3{cam->position[0], cam->position[1], cam->position[2]},
+                     V3{cam->lower_left[0], cam->lower_left[1], cam->lower_left[2]},
+                     V3{cam->horizontal[0], cam->horizontal[1], cam->horizontal[2]},
+                     V3{cam->vertical[0], cam->vertical[1], cam->vertical[2]}};
+  const fr::GbRay r = fr::gb_primary_ray(gc, x, y, W, H);  // (host f32 under the Makefile's numerics rule)
+  *out = fr_ray{{r.o.x, r.o.y, r.o.z}, 0.0f, {r.d.x, r.d.y, r.d.z}, 0.0f};
+  return FR_OK;
+}
+
 int fr_update_delta(uint8_t keys, float dt, float out[3]) {
   if (!out) return set_error(FR_EARG, "fr_update_delta: null output");
   V3 d = mk(0, 0, 0);

@@ -125,6 +125,19 @@ class FrTemporal(C.Structure):
                 ("pad", C.c_uint32 * 4)]
 
 
+class FrRay(C.Structure):
+    _fields_ = [("o", C.c_float * 3), ("pad0", C.c_float), ("d", C.c_float * 3), ("pad1", C.c_float)]
+
+
+class FrCastInfo(C.Structure):
+    _fields_ = [("n", C.c_uint32), ("tree", C.c_uint32), ("waves_tree", C.c_uint32), ("waves_list", C.c_uint32)]
+
+
+# fr_ctx_cast flags (forma_rt.h)
+FR_CAST_LIST = 1
+FR_CAST_RAYS_DEVICE = 2
+
+
 # Every symbol include/forma_rt.h declares (checked by tests/test_abi.py).
 EXPORTS = (
     "fr_last_error", "fr_abi_version", "fr_device_count",
@@ -146,6 +159,7 @@ EXPORTS = (
     "fr_ctx_gbuffer", "fr_ctx_download_gbuffer", "fr_ctx_denoise_guided",
     "fr_camera_axial", "fr_ctx_camera_path", "fr_selftest_camray", "fr_selftest_boxinv",
     "fr_ctx_temporal", "fr_ctx_temporal_reset", "fr_ctx_download_temporal",
+    "fr_ctx_gbuffer_info", "fr_camera_pixel_ray", "fr_ctx_cast", "fr_ctx_download_hits", "fr_ctx_cast_info",
 )
 
 _lib = None
@@ -269,6 +283,12 @@ def lib():
         L.fr_ctx_temporal.argtypes = [vp, C.c_uint32, C.c_float, P(FrDenoiseGuide), P(FrTemporal)]
         L.fr_ctx_temporal_reset.argtypes = [vp]
         L.fr_ctx_download_temporal.argtypes = [vp] + [f3] * 8 + [P(C.c_uint32)] * 2
+    if hasattr(L, "fr_ctx_cast"):
+        L.fr_ctx_gbuffer_info.argtypes = [vp, P(C.c_int)]
+        L.fr_camera_pixel_ray.argtypes = [P(FrCamera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, P(FrRay)]
+        L.fr_ctx_cast.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32]
+        L.fr_ctx_download_hits.argtypes = [vp, P(C.c_uint32), f3, f3, f3, f3]
+        L.fr_ctx_cast_info.argtypes = [vp, P(FrCastInfo)]
     _lib = L
     return L
 
@@ -480,6 +500,14 @@ def camera_orbit(cam, delta):
 def camera_translate(cam, delta):
     check(lib().fr_camera_translate(C.byref(cam), _f3(delta)))
     return cam
+
+
+def pixel_ray(cam, x, y, width, height):
+    """(o [3], d [3]) f32: the pinhole ray of pixel (x, y) of the view, gbuffer()'s
+    (fr_camera_pixel_ray). Needs no device."""
+    r = FrRay()
+    check(lib().fr_camera_pixel_ray(C.byref(cam), int(x), int(y), int(width), int(height), C.byref(r)))
+    return np.array(list(r.o), dtype=np.float32), np.array(list(r.d), dtype=np.float32)
 
 
 def scene_path(name):
@@ -696,8 +724,8 @@ class RenderContext:
     def gbuffer(self, scene, cam, width, height):
         """Enqueues the first-hit feature pass of the view (fr_ctx_gbuffer) and returns at once:
         per pixel the pinhole primary ray's closest primitive, its root, normal, point and
-        albedo. Renders, the accumulation and their outputs are untouched. It tests every
-        primitive for every pixel: once per view, not per frame."""
+        albedo. Renders, the accumulation and their outputs are untouched. A scene with a tree is
+        walked through it (gbuffer_info() says which walk ran); the bits are the list loop's."""
         check(lib().fr_ctx_gbuffer(self._h, scene._h, C.byref(cam), int(width), int(height)))
 
     def download_gbuffer(self, width, height):
@@ -710,6 +738,61 @@ class RenderContext:
         check(lib().fr_ctx_download_gbuffer(self._h, out["prim"].ctypes.data_as(C.POINTER(C.c_uint32)), fp(out["depth"]),
                                             fp(out["normal"]), fp(out["position"]), fp(out["albedo"])))
         return out
+
+    def gbuffer_info(self):
+        """"tree" or "list": the walk the last gbuffer() took (fr_ctx_gbuffer_info). No wait."""
+        t = C.c_int(0)
+        check(lib().fr_ctx_gbuffer_info(self._h, C.byref(t)))
+        return "tree" if t.value else "list"
+
+    def cast(self, scene, origins, directions=None, list_walk=False):
+        """The closest hit of each ray (fr_ctx_cast, fr_ctx_download_hits): origins and directions
+        numpy [n, 3] f32 arrays, or origins a torch tensor [n, 8] f32 on the context's device
+        holding (o, pad, d, pad) per row, complete on the device at the call (directions None).
+        list_walk: the list in order even if the scene has a tree. Returns download_gbuffer()'s
+        dict with "t" for "depth": "prim" [n] uint32 (FR_GBUFFER_MISS for a miss), "t" [n] f32,
+        "normal", "position" and "albedo" [n, 3] f32. Waits for the hits."""
+        flags = FR_CAST_LIST if list_walk else 0
+        if directions is None and hasattr(origins, "data_ptr"):
+            t = origins
+            if t.dim() != 2 or t.shape[1] != 8 or str(t.dtype) != "torch.float32" or not t.is_cuda or not t.is_contiguous():
+                raise ForMaError(FR_EARG, "cast: device rays must be a contiguous float32 [n, 8] tensor on the device")
+            n = int(t.shape[0])
+            check(lib().fr_ctx_cast(self._h, scene._h, C.c_void_p(t.data_ptr()), n, flags | FR_CAST_RAYS_DEVICE))
+        else:
+            o = np.ascontiguousarray(origins, dtype=np.float32)
+            d = np.ascontiguousarray(directions, dtype=np.float32)
+            if o.ndim != 2 or o.shape[1] != 3 or d.shape != o.shape:
+                raise ForMaError(FR_EARG, "cast: origins and directions must be [n, 3] arrays of one length")
+            n = int(o.shape[0])
+            rays = np.zeros((n, 8), dtype=np.float32)
+            rays[:, 0:3] = o
+            rays[:, 4:7] = d
+            check(lib().fr_ctx_cast(self._h, scene._h, rays.ctypes.data_as(C.c_void_p), n, flags))
+        return self.download_hits(n)
+
+    def download_hits(self, n):
+        """The last cast()'s n hits as cast() returns them. Waits for them."""
+        out = {"prim": np.zeros(n, dtype=np.uint32), "t": np.zeros(n, dtype=np.float32)}
+        for name in ("normal", "position", "albedo"):
+            out[name] = np.zeros((n, 3), dtype=np.float32)
+        fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))  # noqa: E731
+        check(lib().fr_ctx_download_hits(self._h, out["prim"].ctypes.data_as(C.POINTER(C.c_uint32)), fp(out["t"]),
+                                         fp(out["normal"]), fp(out["position"]), fp(out["albedo"])))
+        return out
+
+    def cast_info(self):
+        """The last cast() as a dict: "n", "tree" (1: the scene's tree was walked) and the waves of
+        64 rays that walked the tree ("waves_tree") or fell back to the list ("waves_list")."""
+        i = FrCastInfo()
+        check(lib().fr_ctx_cast_info(self._h, C.byref(i)))
+        return {"n": i.n, "tree": i.tree, "waves_tree": i.waves_tree, "waves_list": i.waves_list}
+
+    def pick(self, scene, cam, x, y, width, height):
+        """The list index of the primitive under pixel (x, y) of the view, or None."""
+        o, d = pixel_ray(cam, x, y, width, height)
+        prim = int(self.cast(scene, o[None, :], d[None, :])["prim"][0])
+        return None if prim == FR_GBUFFER_MISS else prim
 
     def download_denoised(self, width, height, want_var=False):
         """(mean [H, W, 3] f32, u8 [H, W, 3]) of the last denoise(), with want_var also the
@@ -802,13 +885,13 @@ class RenderContext:
         """Start (or stop) logging every trace-kernel launch's HIP-event duration."""
         check(lib().fr_ctx_trace_log(self._h, 1 if enable else 0))
 
-    def trace_log_read(self, frames=False, timeline=False, temporal=False):
+    def trace_log_read(self, frames=False, timeline=False, temporal=False, cast=False):
         """HIP-event durations (ms) logged since trace_log(True): every trace-kernel launch,
         or (frames=True) every whole render (trace + sum kernels). timeline=True: (start, end)
         pairs instead, in ms from the first logged trace launch's start. temporal=True: the
         stages of every temporal() call, three durations per call: the prior, totals and prep,
-        the picture."""
-        which = 4 if temporal else (1 if frames else 0) + (2 if timeline else 0)
+        the picture. cast=True: every cast kernel and G-buffer pass."""
+        which = 5 if cast else 4 if temporal else (1 if frames else 0) + (2 if timeline else 0)
         n = C.c_uint32(0)
         check(lib().fr_ctx_trace_log_read(self._h, which, None, 0, C.byref(n)))
         k = 2 if timeline else 1

@@ -66,6 +66,8 @@ extern "C" {
                                fr_denoise_guide, fr_ctx_denoise_guided; fr_camera_axial,
                                fr_ctx_camera_path, fr_selftest_camray, fr_selftest_boxinv; fr_temporal,
                                fr_ctx_temporal, fr_ctx_temporal_reset, fr_ctx_download_temporal) */
+/* (still 6, additive too: fr_ray, fr_cast_info, fr_camera_pixel_ray, fr_ctx_cast, fr_ctx_download_hits,
+   fr_ctx_cast_info, fr_ctx_gbuffer_info; fr_ctx_trace_log_read which = 5) */
 
 /* error codes */
 #define FR_OK 0
@@ -308,7 +310,8 @@ int fr_ctx_device_buffers(fr_ctx* ctx, float** d_mean_rgb, uint8_t** d_rgb8);
    start (2 values per entry, a timeline); which = 4 the stages of every fr_ctx_temporal call,
    three entries per call in order: the prior (reprojection and the copy of the view's G-buffer
    words, or the fills of an empty prior; nothing when the prior is kept), totals and prep, the
-   picture (the levels, or the finalise kernel); *n = the entries logged. Lets a caller
+   picture (the levels, or the finalise kernel); which = 5 every cast kernel (fr_ctx_cast) and
+   G-buffer pass (fr_ctx_gbuffer) enqueued while the log is on; *n = the entries logged. Lets a caller
    streaming K frames average all K of them and see the gaps between them. */
 int fr_ctx_trace_log(fr_ctx* ctx, int enable);
 int fr_ctx_trace_log_read(fr_ctx* ctx, int which, double* ms, uint32_t cap, uint32_t* n);
@@ -444,9 +447,10 @@ int fr_ctx_denoised_buffers(fr_ctx* ctx, float** d_mean_rgb, uint8_t** d_rgb8);
    context's enqueued resolves and returns at once; the buffers are keyed by that upload, the
    camera's 104 bytes, W and H, allocated on first use and kept while the size is unchanged.
    Frames, the accumulation, the outputs of the frames, the pending render and its stats are
-   untouched. The pass tests every primitive of the list for every pixel (no BVH): it is meant
-   to run once per view, not once per frame. FR_EARG for a width or height of 0 and for more than
-   2^27 pixels. */
+   untouched. A scene that has a tree (48 primitives or more, at most 32 planes) is walked through
+   it from a camera within the tree's reach, with the bits of the list loop; smaller scenes and
+   cameras farther out test every primitive of the list for every pixel (fr_ctx_gbuffer_info
+   says which). FR_EARG for a width or height of 0 and for more than 2^27 pixels. */
 #define FR_GBUFFER_MISS 0xFFFFFFFFu
 int fr_ctx_gbuffer(fr_ctx* ctx, fr_scene* scene, const fr_camera* cam, uint32_t width, uint32_t height);
 /* Waits for the last fr_ctx_gbuffer; any pointer may be NULL. prim and depth W*H, normal,
@@ -454,6 +458,41 @@ int fr_ctx_gbuffer(fr_ctx* ctx, fr_scene* scene, const fr_camera* cam, uint32_t 
    (re)allocated. */
 int fr_ctx_download_gbuffer(fr_ctx* ctx, uint32_t* prim, float* depth, float* normal, float* position,
                             float* albedo);
+/* *tree = 1 if the last fr_ctx_gbuffer walked the scene's tree, 0 if the list. The host's record:
+   nothing is waited for. FR_EARG if no G-buffer was enqueued. */
+int fr_ctx_gbuffer_info(fr_ctx* ctx, int* tree);
+
+/* Ray queries: the closest hit of each of the caller's n rays (o, d), through the same
+   closest-hit loop as fr_ctx_gbuffer (list order, t_min = 0.001, t_max = FLT_MAX, strict
+   comparisons, every operation rounded once in f32; fo-rma_amd/csrc/cast.h). A hit is a G-buffer
+   pixel: prim = the winner's list index or FR_GBUFFER_MISS, t = its own accepted root, normal,
+   position = o + t d and albedo; a miss has t 0, normal and position 0 and albedo 1. d is taken as
+   it is (not normalised). A scene that has a tree is walked through it, with the bits of the list
+   loop; FR_CAST_LIST walks the list in order all the same.
+   fr_ctx_cast uploads or reuses the scene's device copy, copies host rays before it returns (the
+   caller may free them), enqueues one kernel behind the context's enqueued resolves and returns at
+   once. The ray and hit buffers are allocated on first use and replaced when n grows. Frames, the
+   accumulation, the outputs, the pending render and its stats, the G-buffer and the temporal
+   history are untouched. FR_EARG, with nothing enqueued, for n = 0, n > 2^27, a NULL pointer or an
+   unknown flag. */
+typedef struct fr_ray { float o[3]; float pad0; float d[3]; float pad1; } fr_ray;      /* 32 bytes; pads ignored */
+typedef struct fr_cast_info { uint32_t n, tree, waves_tree, waves_list; } fr_cast_info; /* tree: 1 if the scene's tree was walked */
+#define FR_CAST_LIST        1u   /* walk the list in order even if the scene has a tree */
+#define FR_CAST_RAYS_DEVICE 2u   /* rays is a device pointer on the context's device, complete at the call,
+                                    valid until fr_ctx_download_hits returns */
+/* The pinhole ray of pixel (x, y) of a W x H view, fr_ctx_gbuffer's: o = position,
+   d = ((lower_left + u horizontal) + v vertical) - position. Host only. FR_EARG for a NULL
+   pointer, W or H of 0, x >= W or y >= H. */
+int fr_camera_pixel_ray(const fr_camera* cam, uint32_t x, uint32_t y, uint32_t W, uint32_t H, fr_ray* out); /* host only */
+int fr_ctx_cast(fr_ctx* ctx, fr_scene* scene, const fr_ray* rays, uint32_t n, uint32_t flags);
+/* Waits for the last fr_ctx_cast; any pointer may be NULL. prim and t n, normal, position and
+   albedo n*3. FR_EARG if nothing was cast since the buffers were (re)allocated. */
+int fr_ctx_download_hits(fr_ctx* ctx, uint32_t* prim, float* t, float* normal, float* position, float* albedo);
+/* The last fr_ctx_cast: its n, whether the tree was walked, and the waves (64 rays) that walked
+   the tree and that fell back to the list (a wave with a ray whose origin lies beyond the tree's
+   reach or is NaN, whose direction is below 2^-70 in every component, or whose o / d overflows,
+   walks the list for all its rays); the two sum to ceil(n / 64). */
+int fr_ctx_cast_info(fr_ctx* ctx, fr_cast_info* out);   /* waits, like the download */
 
 /* Feature-guided denoise of the live accumulation: fr_ctx_denoise's a-trous filter with every
    non-centre tap's weight extended by the G-buffer of the same view.

@@ -1,8 +1,13 @@
 """Times of the G-buffer pass (fr_ctx_gbuffer) and of the feature-guided filter
 (fr_ctx_denoise_guided) at 1920x1080.
 
-- The G-buffer pass of scene_08 (6 boxes) and of the 10,000-sphere generator scene (BASELINE
-  config C5): a list loop over every primitive for every pixel.
+- The G-buffer pass of scene_08 (6 boxes: the list loop) and of the 10,000-sphere generator scene
+  (BASELINE config C5) through its tree (gbuffer_tree_kernel) and, in the same run and
+  alternating, through the list loop over every primitive for every pixel. The tool picks the walk
+  for itself through the environment switch FR_GBUFFER_WALK=tree / list (read by fr_ctx_gbuffer
+  at every call), times both by the launch log's HIP events too (fr_ctx_trace_log_read, which =
+  5), counts the pixels whose bits differ between the two passes and holds the list pass's
+  digest against the recorded one.
 - The guided filter at the defaults (levels 4, k 4) on eight accumulating 16-spp frames of
   scene_08, and the unguided filter (fr_ctx_denoise) in the same run, the two alternating.
 
@@ -32,6 +37,8 @@ sys.path.insert(0, os.path.join(ROOT, "fo-rma_amd"))
 import forma_rt as fr  # noqa: E402
 
 DEPTH, SEED = 8, 0xD100
+LIST_DIGEST = "691d200294e3cec5"  # profiles/gbuffer_1080p.json gbuffer_spheres_sha256_16 (10,000 spheres at 1920x1080)
+WALK_ENV = "FR_GBUFFER_WALK"
 HEADLINE_FRAME_MS, C5_FRAME_MS, UNGUIDED_MS = 14.06, 39.2, 0.24  # profiles/r06ai_bench.json, README, profiles/denoise_1080p.json
 
 
@@ -65,6 +72,24 @@ def digest(g):
     return hashlib.sha256(b"".join(g[k].tobytes() for k in ("prim", "depth", "normal", "position", "albedo"))).hexdigest()[:16]
 
 
+def set_walk(walk):
+    """The walk the following fr_ctx_gbuffer calls of this process take: "tree", "list" or None
+    for the library's default."""
+    if walk is None:
+        os.environ.pop(WALK_ENV, None)
+    else:
+        os.environ[WALK_ENV] = walk
+
+
+def differing_pixels(a, b):
+    bad = None
+    for k in ("prim", "depth", "normal", "position", "albedo"):
+        x, y = a[k].view("uint32"), b[k].view("uint32")
+        d = (x != y) if x.ndim == 2 else (x != y).any(axis=2)
+        bad = d if bad is None else bad | d
+    return int(bad.sum())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--width", type=int, default=1920)
@@ -86,10 +111,38 @@ def main():
 
     # the 10,000-sphere list: one call per group member is tens of ms, so fewer calls per group
     big = fr.Scene.from_json(gen_spheres(a.spheres), w, h)
+    set_walk(None)
     ctx.gbuffer(big, big.camera, w, h)
     wait_gb()
-    c5 = groups_ms(lambda: ctx.gbuffer(big, big.camera, w, h), wait_gb, max(1, a.calls // 5), a.groups)
+    default_walk = ctx.gbuffer_info()
+    big_call = lambda: ctx.gbuffer(big, big.camera, w, h)  # noqa: E731
+    tree, lst, walks = [], [], {}
+    for _ in range(3):  # the two alternating: the same machine state for both
+        for walk, out, calls in (("tree", tree, a.calls), ("list", lst, max(1, a.calls // 5))):
+            set_walk(walk)
+            big_call()
+            wait_gb()
+            walks[walk] = ctx.gbuffer_info()
+            out += groups_ms(big_call, wait_gb, calls, a.groups // 2 + 1)
+    # the same two passes by the launch log's events, alternating call by call
+    ctx.trace_log(True)
+    for _ in range(a.groups + 1):
+        for walk in ("tree", "list"):
+            set_walk(walk)
+            big_call()
+    ev = ctx.trace_log_read(cast=True)
+    ctx.trace_log(False)
+    ev_tree, ev_list = ev[2::2], ev[3::2]  # (the first pair is a warm-up)
+    set_walk("list")
+    big_call()
+    g_list = ctx.download_gbuffer(w, h)
+    set_walk("tree")
+    big_call()
+    g_tree = ctx.download_gbuffer(w, h)
+    set_walk(None)
+    big_call()
     g_big = ctx.download_gbuffer(w, h)
+    c5 = tree if default_walk == "tree" else lst
     hit_big = int((g_big["prim"] != fr.FR_GBUFFER_MISS).sum())
 
     sc = fr.Scene.from_file(fr.scene_path("scene_08"), w, h)
@@ -98,6 +151,7 @@ def main():
     ctx.sync()
     ctx.gbuffer(sc, sc.camera, w, h)
     wait_gb()
+    s08_walk = ctx.gbuffer_info()
     s08 = groups_ms(lambda: ctx.gbuffer(sc, sc.camera, w, h), wait_gb, a.calls, a.groups)
     g_s08 = ctx.download_gbuffer(w, h)
     levels, kk = fr.FR_DN_LEVELS_DEFAULT, fr.FR_DN_K_DEFAULT
@@ -116,10 +170,22 @@ def main():
     guided_call()
     mean, u8, var = ctx.download_denoised(w, h, want_var=True)
     gd, pl, s8, c5s = summary(guided), summary(plain), summary(s08), summary(c5)
+    trs, lss = summary(tree), summary(lst)
+    diff = differing_pixels(g_tree, g_list)
     res = {"what": "fr_ctx_gbuffer and fr_ctx_denoise_guided, host wall time of `calls` enqueues plus one wait over `calls`",
            "shape": [w, h], "calls": a.calls, "groups": a.groups,
            "gbuffer_scene_08_ms": s8["median"], "gbuffer_scene_08_spread": [s8["min"], s8["max"]],
            "gbuffer_spheres": a.spheres, "gbuffer_spheres_ms": c5s["median"], "gbuffer_spheres_spread": [c5s["min"], c5s["max"]],
+           "gbuffer_spheres_default_walk": default_walk, "gbuffer_scene_08_walk": s08_walk,
+           "gbuffer_spheres_walks_forced": walks,
+           "gbuffer_spheres_tree_ms": trs["median"], "gbuffer_spheres_tree_spread": [trs["min"], trs["max"]],
+           "gbuffer_spheres_list_ms": lss["median"], "gbuffer_spheres_list_spread": [lss["min"], lss["max"]],
+           "gbuffer_spheres_list_over_tree": round(lss["median"] / trs["median"], 2),
+           "gbuffer_spheres_tree_event_ms": summary(ev_tree), "gbuffer_spheres_list_event_ms": summary(ev_list),
+           "gbuffer_spheres_differing_pixels": diff,
+           "gbuffer_spheres_tree_sha256_16": digest(g_tree), "gbuffer_spheres_list_sha256_16": digest(g_list),
+           "gbuffer_spheres_list_sha256_16_recorded": LIST_DIGEST,
+           "tree_is_default_by_rule": bool(diff == 0 and trs["median"] < lss["min"]),
            "gbuffer_spheres_hit_pixels": hit_big, "sphere_tests": a.spheres * w * h,
            "sphere_tests_per_s": round(a.spheres * w * h / (c5s["median"] * 1e-3), 0),
            "c5_frame_ms": C5_FRAME_MS, "gbuffer_spheres_over_c5_frame": round(c5s["median"] / C5_FRAME_MS, 3),
@@ -141,6 +207,8 @@ def main():
         with open(a.out, "w") as f:
             json.dump(res, f, indent=1)
             f.write("\n")
+    if (w, h, a.spheres) == (1920, 1080, 10000) and digest(g_list) != LIST_DIGEST:
+        raise SystemExit(f"gbuffer_time: the list pass's digest {digest(g_list)} is not the recorded {LIST_DIGEST}")
 
 
 if __name__ == "__main__":
