@@ -36,12 +36,14 @@ struct Box3 {
 
 // World bounds of one primitive; false for primitives that never hit (stubs) or
 // carry non-finite geometry (those stay out of the tree and can never be the winner
-// of the list loop either: their tests compare NaN).
-bool prim_bounds(const fr_prim& p, Box3& b) {
+// of the list loop either: their tests compare NaN). `reach` < 0: a sphere's own ball (the
+// scene's extent is taken from those); otherwise the ball its test accepts roots in for origins
+// within `reach` (bvh.h bvh_sphere_bound), which the tree is built over.
+bool prim_bounds(const fr_prim& p, Box3& b, float reach = -1.0f) {
   const float* g = p.g;
   switch (p.kind) {
     case FR_SPHERE: {
-      const float r = fabsf(g[3]);
+      const float r = reach < 0.0f ? fabsf(g[3]) : bvh_sphere_bound(g, fabsf(g[3]), reach);
       const float lo[3] = {g[0] - r, g[1] - r, g[2] - r}, hi[3] = {g[0] + r, g[1] + r, g[2] + r};
       b.grow(lo);
       b.grow(hi);
@@ -281,13 +283,13 @@ float scene_abs_max(const std::vector<fr_prim>& prims) {
 
 // Builds the tree over the boundable primitives of prims[begin, end); `root` is its
 // reference (kBvhEnd when none is boundable). False if it cannot be encoded.
-bool build_range(const std::vector<fr_prim>& prims, uint32_t begin, uint32_t end, float pad,
+bool build_range(const std::vector<fr_prim>& prims, uint32_t begin, uint32_t end, float pad, float reach,
                  std::vector<BvhNode>& nodes, std::vector<uint32_t>& order, uint32_t& root) {
   std::vector<Item> items;
   items.reserve(end - begin);
   for (uint32_t i = begin; i < end; ++i) {
     Item it;
-    if (!prim_bounds(prims[i], it.box)) continue;
+    if (!prim_bounds(prims[i], it.box, reach)) continue;
     for (int k = 0; k < 3; ++k) it.c[k] = 0.5f * (it.box.lo[k] + it.box.hi[k]);
     it.index = i;
     items.push_back(it);
@@ -344,6 +346,9 @@ bool build_segments(const std::vector<fr_prim>& prims, std::vector<BvhSegment>& 
   const float ext = scene_abs_max(prims);
   if (extent) *extent = ext;
   const float pad = 1e-4f * ext + 1e-4f;
+  // a sphere's test accepts, by its discriminant's rounding error, rays that pass outside it:
+  // its bounds are those of the larger ball that holds every such root from within the reach
+  const float reach = bvh_origin_reach(ext, bvh_sphere_rmin(prims));
   uint32_t i = 0;
   while (i < n) {
     if (prims[i].kind == FR_PLANE) {
@@ -354,11 +359,21 @@ bool build_segments(const std::vector<fr_prim>& prims, std::vector<BvhSegment>& 
     uint32_t j = i;
     while (j < n && prims[j].kind != FR_PLANE) ++j;
     uint32_t root = kBvhEnd;
-    if (!build_range(prims, i, j, pad, nodes, order, root)) return false;
+    if (!build_range(prims, i, j, pad, reach, nodes, order, root)) return false;
     if (root != kBvhEnd) segs.push_back(BvhSegment{0u, root, 0u, 0u});
     i = j;
   }
   return true;
+}
+
+float bvh_sphere_rmin(const std::vector<fr_prim>& prims) {
+  float rmin = -1.0f;
+  for (const fr_prim& p : prims)
+    if (p.kind == FR_SPHERE) {
+      const float r = fabsf(p.g[3]);
+      if (rmin < 0.0f || !(r >= rmin)) rmin = r == r ? r : 0.0f;
+    }
+  return rmin;
 }
 
 uint32_t bvh_max_depth(const std::vector<BvhSegment>& segs, const std::vector<BvhNode>& nodes) {

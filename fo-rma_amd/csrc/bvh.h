@@ -73,8 +73,9 @@ constexpr uint32_t kBvhMaxPlanes = 32;  // more planes: the in-order loop
 // Segments, nodes and the leaf-order primitive list (`order[slot]` = list index) for a
 // scene; false if the scene is too small, has too many planes or is too large for the
 // reference encoding. `force` drops the size and cost thresholds (A/B runs).
-// `extent` (if given) receives the largest |coordinate| of any primitive's bounds: the
-// boxes are padded by 1e-4 * (extent + 1).
+// `extent` (if given) receives the largest |coordinate| of any primitive's own bounds: the
+// boxes are padded by 1e-4 * (extent + 1), and a sphere is bounded by bvh_sphere_bound at the
+// scene's reach (bvh_origin_reach of that extent and the smallest radius).
 bool build_segments(const std::vector<fr_prim>& prims, std::vector<BvhSegment>& segs, std::vector<BvhNode>& nodes,
                     std::vector<uint32_t>& order, bool force = false, float* extent = nullptr);
 #endif
@@ -89,27 +90,73 @@ constexpr float kBvhOriginReach = 100.0f;
 // zero direction component (inv = +-inf) would make fma(lo, inv, -o inv) NaN. A clamped
 // slab is conservative while the hit's t is far below its width: a hit inside a box padded by
 // >= 1e-4 (extent + 1) keeps that axis's slab >= 1e-4 (extent + 1) 2^100 wide about the
-// origin, and a direction with one component of 2^-70 or more has every hit at
-// t <= 101 (extent + 1) 2^70. A direction that is tiny in every component (hits at
-// t ~ 2^100, clamped or not) takes the in-order loop: kBvhTinyDir, the kernel's list_walk
-// ballot, which also sends an overflowing o inv (|o| >= 2^28 with a clamped component) there.
+// origin, and a direction with one component of 2^-60 or more has every hit at
+// t <= 101 (extent + 1) 2^60. A direction that is tiny in every component takes the in-order
+// loop: kBvhTinyDir, the kernel's list_walk ballot, which also sends an overflowing o inv
+// (|o| >= 2^28 with a clamped component) there. The limit is 2^-60 and not the 2^-70 the clamp
+// alone would allow because of the sphere test: below it dot(d, d) < 2^-120 and the products of
+// the discriminant lose their relative accuracy to underflow (at |d| ~ 2^-69 b b and a c are
+// denormals of a few ulps and the test accepts rays that pass a sphere far outside any
+// padding). At 2^-60 the underflow is bounded by kSphereDiscAbs below.
 constexpr float kBvhInvClamp = 0x1p100f;
-constexpr float kBvhTinyDir = 0x1p-70f;
+constexpr float kBvhTinyDir = 0x1p-60f;
 
 #if !defined(__HIPCC_RTC__)
-// The reach for a scene: kBvhOriginReach extents, less for a scene with spheres. The sphere
-// test's discriminant b b - a c carries a rounding error of up to 15 * 2^-24 |o - c|^2 a
-// (three-term dot products, the two products and the difference), so from far away it accepts
-// rays that pass the sphere at a distance of up to sqrt(r^2 + E) with
-// E = 2^-20 |o - c|^2, and the cull must not reject what the test accepts. Half of the padding
-// covers that for |o - c|^2 <= 3 (|o| + extent)^2 while E <= r pad + pad^2 / 4, r the
-// smallest radius. The reach is never set below extent + 1, because every scatter origin
-// lies there and a shorter reach would switch the BVH off: that floor is a policy, not a
-// bound. Where extent is more than about 10 r (the test lattices; 10,000 spheres of radius
-// 2.5 over +-5000) the derived distance is below the floor, and inside the floor the test can
-// still accept a far sphere by rounding error that the cull rejects. No frame of the suite
-// shows it (such a far "hit" lies behind nearer ones almost always); closing it needs sphere
-// bounds padded by the test's own error, which is not done here.
+// What the sphere test accepts, and the bounds that follow from it. sphere_root_rr (rt_core.h)
+// accepts when RN(b b) > RN(a cc) (the difference of two floats has its exact sign), with
+// oc = RN(o - c), b = dot(oc, d), cc = RN(dot(oc, oc) - rr), a = dot(d, d), every dot product
+// three rounded products and two rounded sums. With u = 2^-24, L = |o - c|, D = |d| and p the
+// ray's distance from the centre (a (p^2 - r^2) = a cc - b b exactly), to first order in u:
+//   oc        u per component
+//   b         4 u L D (oc 1, product 1, sums 2)       RN(b b) <= b^2 + 9 u L^2 D^2
+//   dot(oc,oc) 5 u L^2 (oc 2, product 1, sums 2); rr u r^2; the subtraction u (L^2 - r^2)
+//                                                     cc >= L^2 - r^2 - 6 u L^2
+//   a         3 u D^2; the product a cc one more u    RN(a cc) >= a (L^2 - r^2) - 10 u L^2 D^2
+// so an accepted ray has p^2 - r^2 < 19 u L^2, the second-order terms (~100 u^2 L^2) and the
+// underflow of a direction at the tiny limit included in
+//   p^2 < r^2 + kSphereDiscErr L^2 + kSphereDiscAbs,   kSphereDiscErr = 20 * 2^-24.
+// Underflow: an operation that underflows errs by U = 2^-150 at most. The three products of a,
+// the three of b, and b b and a cc add U (2 + 3 L^2 + 6 L D) to a (p^2 - r^2); with one direction
+// component of kBvhTinyDir = 2^-60 or more, a >= 2^-120, which is 2^-29 + 0.05 u L^2 + 6 L 2^-90 in
+// p^2: kSphereDiscAbs = 2^-28 and the slack of 20 over 19 hold it. (The bound assumes no
+// overflow: L D < 2^63, far beyond any scene the padding's own arithmetic holds for.)
+// The accepted root lies on the chord of that larger ball: sq^2 = disc <= a (r^2 + E - p^2), so
+// the hit point is within sqrt(r^2 + E) of the centre, up to the root's own rounding (a few
+// u L), which the boxes' padding covers as it does for every kind's roots.
+constexpr float kSphereDiscErr = 20.0f * 0x1p-24f;
+constexpr float kSphereDiscAbs = 0x1p-28f;
+// The radius of the ball every accepted root of a sphere (centre c, radius r) lies in, for
+// every ray the walk admits: origin components within `reach` (cast_fallback's first
+// condition, so |o_k - c_k| <= reach + |c_k|) and a direction component of kBvhTinyDir or more.
+// The builder bounds a sphere by c +- this. Formed in double and rounded up.
+inline float bvh_sphere_bound(const float c[3], float r, float reach) {
+  double l2 = 0.0;
+  for (int k = 0; k < 3; ++k) {
+    const double l = static_cast<double>(reach) + fabs(static_cast<double>(c[k]));
+    l2 += l * l;
+  }
+  const double R = sqrt(static_cast<double>(r) * r + static_cast<double>(kSphereDiscErr) * l2 + kSphereDiscAbs);
+  float f = static_cast<float>(R);
+  if (static_cast<double>(f) < R) f = nextafterf(f, INFINITY);
+  return f;
+}
+
+// The reach for a scene: kBvhOriginReach extents, less for a scene with spheres, whose bounds
+// grow with it (bvh_sphere_bound: E = kSphereDiscErr |o - c|^2 is added to r^2). It is chosen
+// so that E stays within r pad + pad^2 / 4 (r the smallest radius, pad the boxes' padding, with
+// 2^-20 for the constant and |o - c|^2 <= 3 (|o| + extent)^2): up to there a sphere's bounds
+// grow by less than half the padding. The reach is never set below extent + 1, because every
+// scatter origin lies there and a shorter reach would switch the BVH off. Where extent is more
+// than about 10 r (the test lattices; 10,000 spheres of radius 2.5 over +-5000) the floor
+// decides, and the bounds of a small sphere grow by more than its radius: at the floor
+// sqrt(E) <= sqrt(60 * 2^-24) (2 extent + 1) = 0.0038 extent. The generator's 10,000 spheres of
+// radius 2.5 (a 10 x 1000 grid at a spacing of 5, extent 4997.5) get bounds of radius 9.8 to
+// 13.6, which overlap several neighbours a side: its trace costs 2.3 times what it did with
+// bounds of 2.5. The scalar reach is a cube, so x and z count 5000 units each
+// for a scene 50 wide and 5 deep; a reach per axis would cut those bounds to a radius of 4 to 6
+// and is not done here (it changes the kernels' fallback test). The reach is a policy for the
+// boxes' size; the cull is conservative for any reach the bounds were built with
+// (tests/test_cull_host.py).
 inline float bvh_origin_reach(float extent, float sphere_rmin) {
   const float unit = extent + 1.0f;
   float reach = kBvhOriginReach * unit;
@@ -120,6 +167,9 @@ inline float bvh_origin_reach(float extent, float sphere_rmin) {
   }
   return reach;
 }
+// The smallest sphere radius of a list (-1: no sphere; a NaN radius counts as 0): the second
+// argument of bvh_origin_reach, SceneFacts::bvh_sphere_rmin.
+float bvh_sphere_rmin(const std::vector<fr_prim>& prims);
 #endif
 
 #if !defined(__HIPCC_RTC__)

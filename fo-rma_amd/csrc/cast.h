@@ -8,8 +8,9 @@
 // BvhSegments, in order. A plane is tested where it stands against `closest`. A run yields the
 // least (t, index) of the run below `closest`: a leaf primitive is tested with t_max = closest,
 // or one ulp above closest when its index is below the current winner's (it may take an exact
-// tie), and the node boxes are padded, so nothing the list loop accepts is culled while the three
-// conditions of cast_fallback hold; a ray that fails one takes the list.
+// tie), and the node boxes are padded over bounds that hold each test's own error (a sphere's:
+// bvh.h bvh_sphere_bound), so nothing the list loop accepts is culled while the three conditions of
+// cast_fallback hold; a ray that fails one takes the list.
 #pragma once
 #include <float.h>
 

@@ -86,11 +86,7 @@ PackedScene pack_scene(const std::vector<fr_prim>& prims, bool force_bvh) {
   sf.n = n;
   sf.bvh_ok = bvh_ok;
   sf.bvh_extent = bvh_extent;
-  for (const fr_prim& p : prims)
-    if (p.kind == FR_SPHERE) {
-      const float r = fabsf(p.g[3]);
-      if (sf.bvh_sphere_rmin < 0.0f || !(r >= sf.bvh_sphere_rmin)) sf.bvh_sphere_rmin = r == r ? r : 0.0f;
-    }
+  sf.bvh_sphere_rmin = bvh_sphere_rmin(prims);
   sf.n_segs = static_cast<uint32_t>(bvh_segs.size());
   sf.bvh_levels = bvh_ok ? std::min(bvh_max_depth(bvh_segs, bvh_nodes) + 1u, kBvhStack) : kBvhStack;
   for (uint32_t i = 0; i < n; ++i) {

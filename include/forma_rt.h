@@ -490,7 +490,7 @@ int fr_ctx_cast(fr_ctx* ctx, fr_scene* scene, const fr_ray* rays, uint32_t n, ui
 int fr_ctx_download_hits(fr_ctx* ctx, uint32_t* prim, float* t, float* normal, float* position, float* albedo);
 /* The last fr_ctx_cast: its n, whether the tree was walked, and the waves (64 rays) that walked
    the tree and that fell back to the list (a wave with a ray whose origin lies beyond the tree's
-   reach or is NaN, whose direction is below 2^-70 in every component, or whose o / d overflows,
+   reach or is NaN, whose direction is below 2^-60 in every component, or whose o / d overflows,
    walks the list for all its rays); the two sum to ceil(n / 64). */
 int fr_ctx_cast_info(fr_ctx* ctx, fr_cast_info* out);   /* waits, like the download */
 

@@ -10,10 +10,13 @@
 // root bits differ. It also checks, for every pixel of the W x H view, that cast_ray of the
 // pixel ray's o and d has the bits of gb_primary_ray, and, for every leaf slot, that a sphere's
 // leaf-order record carries the product RN(r r) that sphere_root forms from the list record.
-// Prints one line
-//   info tree T segs S nodes N levels L reach R(hex) fallback F steps K mismatch M pixel_ray P rr Q
+// For every ray that passes cast_fallback and whose list winner is a sphere, it checks in double
+// that the ray passes the centre within bvh_sphere_bound (bvh.h), the ball the builder bounds the
+// sphere by. Prints one line
+//   info tree T segs S nodes N levels L reach R(hex) fallback F steps K mismatch M pixel_ray P rr Q bound B
 // then one line per ray in hex: the list loop's id, the bits of t, N, P and the albedo (11 words),
-// and a 12th word, 1 if the ray falls back. Exit status 1 if M, P or Q is not 0.
+// and a 12th word, 1 if the ray falls back. Exit status 1 if M, P, Q or B is not 0.
+#include <math.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
@@ -128,7 +131,7 @@ int main(int argc, char** argv) {
     }
   }
 
-  uint32_t n_fallback = 0, mismatch = 0;
+  uint32_t n_fallback = 0, mismatch = 0, bad_bound = 0;
   unsigned long long steps = 0;
   std::vector<uint32_t> lines(static_cast<size_t>(m) * 12);
   for (uint32_t q = 0; q < m; ++q) {
@@ -151,6 +154,15 @@ int main(int argc, char** argv) {
         ++mismatch;
       }
     }
+    if (!fb && best >= 0 && prims[best].kind == FR_SPHERE) {
+      // the distance at which the ray passes the winner's centre: |oc x d| / |d|
+      const float* g = prims[best].g;
+      const double oc[3] = {static_cast<double>(r.o.x) - g[0], static_cast<double>(r.o.y) - g[1], static_cast<double>(r.o.z) - g[2]};
+      const double dd[3] = {r.d.x, r.d.y, r.d.z};
+      const double cx[3] = {oc[1] * dd[2] - oc[2] * dd[1], oc[2] * dd[0] - oc[0] * dd[2], oc[0] * dd[1] - oc[1] * dd[0]};
+      const double pass = sqrt((cx[0] * cx[0] + cx[1] * cx[1] + cx[2] * cx[2]) / (dd[0] * dd[0] + dd[1] * dd[1] + dd[2] * dd[2]));
+      if (!(pass <= static_cast<double>(fr::bvh_sphere_bound(g, fabsf(g[3]), reach)))) ++bad_bound;
+    }
     fr::GbPixel p = fr::gb_miss();
     if (best >= 0) {
       const fr::CastRec rec{tb.rec + 16 * static_cast<size_t>(best)};
@@ -161,12 +173,12 @@ int main(int argc, char** argv) {
                                bits(p.g1.y), bits(p.g1.z), bits(p.alb.x), bits(p.alb.y), bits(p.alb.z), fb ? 1u : 0u};
     memcpy(&lines[12 * static_cast<size_t>(q)], line, sizeof(line));
   }
-  printf("info tree %u segs %u nodes %u levels %u reach %08x fallback %u steps %llu mismatch %u pixel_ray %u rr %u\n",
-         tree ? 1u : 0u, tb.n_segs, n_nodes, ps.facts.bvh_levels, bits(reach), n_fallback, steps, mismatch, bad_pixel, bad_rr);
+  printf("info tree %u segs %u nodes %u levels %u reach %08x fallback %u steps %llu mismatch %u pixel_ray %u rr %u bound %u\n",
+         tree ? 1u : 0u, tb.n_segs, n_nodes, ps.facts.bvh_levels, bits(reach), n_fallback, steps, mismatch, bad_pixel, bad_rr, bad_bound);
   for (uint32_t q = 0; q < m; ++q) {
     const uint32_t* l = &lines[12 * static_cast<size_t>(q)];
     printf("%08x %08x %08x %08x %08x %08x %08x %08x %08x %08x %08x %u\n", l[0], l[1], l[2], l[3], l[4], l[5], l[6], l[7], l[8],
            l[9], l[10], l[11]);
   }
-  return mismatch || bad_pixel || bad_rr ? 1 : 0;
+  return mismatch || bad_pixel || bad_rr || bad_bound ? 1 : 0;
 }

@@ -29,7 +29,7 @@ from tests import ray_edge_fixtures as X
 F = np.float32
 MISS = G.MISS
 SEED = 0xCA57
-TINY_DIR = F(2.0 ** -70)      # bvh.h kBvhTinyDir
+TINY_DIR = F(2.0 ** -60)      # bvh.h kBvhTinyDir
 INV_CLAMP = F(2.0 ** 100)     # rt_core.h kBoxInvClamp, bvh.h kBvhInvClamp
 REACH_UNITS = 100.0           # bvh.h kBvhOriginReach
 
@@ -143,7 +143,7 @@ def fallback_terms(o, d, reach_lo, reach_hi):
     """cast.h's three fallback conditions per ray, each as a ([n] bool "true for sure", [n] bool
     "false for sure") pair: the origin test against a reach known only to lie in [reach_lo,
     reach_hi]. A NaN component of o fails the first and the third; the second asks for one
-    direction component of 2^-70 or more."""
+    direction component of 2^-60 or more."""
     o, d = np.asarray(o, F), np.asarray(d, F)
     with np.errstate(all="ignore"):
         ad = np.fmax.reduce(np.abs(d), axis=1)

@@ -109,15 +109,19 @@ def test_generator_scene_bvh_build_clean(exe, tmp_path):
     # launch sizes its LDS stack to depth + 1 levels), leaves of at most 4 spheres
     assert r["bvh"]["depth"] < 16 and 10000 / 4 - 1 <= r["bvh"]["nodes"] < 10000
     # the tree the C5 timings were taken on (round 5's sort-per-node builder built the same
-    # bytes: nodes, leaf order, segments); a builder change that moves it shows here
-    assert r["bvh"]["digest"] == "74bc9267b6b5e9e6", r["bvh"]
+    # bytes: nodes, leaf order, segments); a builder change that moves it shows here. Re-pinned
+    # (from 74bc9267b6b5e9e6) when spheres came to be bounded by bvh_sphere_bound: wider boxes, and
+    # the splits that follow from them
+    assert r["bvh"]["digest"] == "3ef837e2547dc637", r["bvh"]
 
 
 # forced trees of the bundled scenes (fnv-1a over nodes, leaf order and segments), equal for
-# round 5's builder (sorting every node's items per axis) and round 6's (presorted orders)
+# round 5's builder (sorting every node's items per axis) and round 6's (presorted orders).
+# scene_01 and scene_05, the two with spheres, were re-pinned (from db0be86289f89f8d and
+# 8ee866288e39c8d0) when a sphere's bounds became bvh_sphere_bound's; the others did not move.
 BUNDLED_TREE_DIGESTS = {
-    "scene_01": "db0be86289f89f8d", "scene_02": "9402547a91b47399", "scene_03": "346a873c38c9159b",
-    "scene_04": "51895897d1998ae2", "scene_05": "8ee866288e39c8d0", "scene_06": "191d4432c7c74f33",
+    "scene_01": "bca0bc7a13e0e1ba", "scene_02": "9402547a91b47399", "scene_03": "346a873c38c9159b",
+    "scene_04": "51895897d1998ae2", "scene_05": "38c997c4c743a5c8", "scene_06": "191d4432c7c74f33",
     "scene_08": "3a4d7944ad02b602", "scene_09": "6f417d5af3a20a2f",
 }
 
