@@ -11,6 +11,10 @@
 // tie), and the node boxes are padded over bounds that hold each test's own error (a sphere's:
 // bvh.h bvh_sphere_bound), so nothing the list loop accepts is culled while the three conditions of
 // cast_fallback hold; a ray that fails one takes the list.
+//
+// Ranged casts and occlusion queries (fr_ctx_occluded): the walks take the ray's
+// t_max as what `closest` starts at, and occl_walk_list / occl_walk_tree answer whether any
+// primitive's test accepts the ray within (kGbTMin, t_max) (occlude.hip, tests/c/occlude_check.cpp).
 #pragma once
 #include <float.h>
 
@@ -147,9 +151,11 @@ inline uint32_t cast_rec_kind(const float* w) {
   return k;
 }
 
-// The list loop: the definition every walk must equal.
-inline void cast_walk_list(const CastTables& s, const GbRay& r, float& closest, int& best) {
-  closest = kCastTMax;
+// The list loop: the definition every walk must equal. t_max: the ray's range (kGbTMin, t_max),
+// what `closest` starts at; whatever a NaN, an infinity, 0 or a negative gives in
+// the comparisons below is the answer.
+inline void cast_walk_list(const CastTables& s, const GbRay& r, float& closest, int& best, float t_max = kCastTMax) {
+  closest = t_max;
   best = -1;
   for (uint32_t rr = 0; rr < s.n_runs; ++rr) {
     const uint32_t k = s.runs[4 * rr], i0 = s.runs[4 * rr + 1], i1 = s.runs[4 * rr + 2];
@@ -164,9 +170,11 @@ inline void cast_walk_list(const CastTables& s, const GbRay& r, float& closest, 
 }
 
 // The tree walk as a definition: segments in order, near child first, the far child stacked.
-// steps (if given) receives the node steps taken.
-inline void cast_walk_tree(const CastTables& s, const GbRay& r, float& closest, int& best, uint32_t* steps = nullptr) {
-  closest = kCastTMax;
+// steps (if given) receives the node steps taken. t_max: as cast_walk_list's (the node cull and
+// cast_leaf_tmax are written against `closest`, whatever it starts at).
+inline void cast_walk_tree(const CastTables& s, const GbRay& r, float& closest, int& best, uint32_t* steps = nullptr,
+                           float t_max = kCastTMax) {
+  closest = t_max;
   best = -1;
   const CastCull c = cast_cull(r);
   uint32_t nsteps = 0;
@@ -209,6 +217,62 @@ inline void cast_walk_tree(const CastTables& s, const GbRay& r, float& closest, 
   }
   if (steps) *steps = nsteps;
 }
+
+// Occlusion (any hit): the OR over every list primitive of its test against
+// t_max itself. It equals "cast_walk_list(.., t_max) finds a winner": the first primitive that
+// loop accepts was tested against t_max, and one that passes at t_max is accepted or preceded by
+// one that was. Being an OR, the order of the tests is free and a walk may stop at the first.
+inline bool occl_walk_list(const CastTables& s, const GbRay& r, float t_max) {
+  bool occ = false;
+  for (uint32_t rr = 0; rr < s.n_runs; ++rr) {
+    const uint32_t k = s.runs[4 * rr], i0 = s.runs[4 * rr + 1], i1 = s.runs[4 * rr + 2];
+    for (uint32_t i = i0; i < i1; ++i) {
+      float t = 0.0f;
+      occ |= cast_list_test(k, CastRec{s.rec + 16 * static_cast<size_t>(i)}, r, t_max, t);
+    }
+  }
+  return occ;
+}
+
+// The any-hit tree walk as a definition: segments in order, a plane where it stands against
+// t_max, a run from its root with the node cull at closest = t_max and its leaves tested against
+// t_max; returns at the first accepted test. steps (if given) receives the node steps taken.
+inline bool occl_walk_tree(const CastTables& s, const GbRay& r, float t_max, uint32_t* steps = nullptr) {
+  const CastCull c = cast_cull(r);
+  uint32_t nsteps = 0;
+  bool occ = false;
+  for (uint32_t sg = 0; sg < s.n_segs && !occ; ++sg) {
+    const BvhSegment& seg = s.segs[sg];
+    float t = 0.0f;
+    if (seg.plane) {
+      occ = gb_test<FR_PLANE>(CastRec{s.rec + 16 * static_cast<size_t>(seg.prim)}, r, t_max, t);
+      continue;
+    }
+    uint32_t stack[kBvhStack + 1];
+    uint32_t sp = 0;
+    stack[sp++] = kBvhEnd;  // the sentinel
+    uint32_t ref = seg.root;
+    while (ref != kBvhEnd && !occ) {
+      if (ref < kBvhLeaf) {
+        const BvhNode& nd = s.nodes[ref];
+        const CastStep st = cast_node_step(GbF4{nd.a[0], nd.a[1], nd.a[2], nd.a[3]}, GbF4{nd.b[0], nd.b[1], nd.b[2], nd.b[3]},
+                                           GbF4{nd.c[0], nd.c[1], nd.c[2], nd.c[3]}, nd.ref[0], nd.ref[1], c, t_max);
+        ++nsteps;
+        if (st.both) stack[sp++] = st.far;
+        ref = st.any ? st.near : stack[--sp];
+        continue;
+      }
+      const uint32_t first = ref & ((1u << kBvhSlotBits) - 1u), cnt = ((ref >> kBvhSlotBits) & 15u) + 1u;
+      for (uint32_t k = 0; k < cnt && !occ; ++k) {
+        const float* lw = s.lrec + 16 * static_cast<size_t>(first + k);
+        occ = cast_leaf_test(cast_rec_kind(lw), CastRec{lw}, r, t_max, t);
+      }
+      ref = stack[--sp];
+    }
+  }
+  if (steps) *steps = nsteps;
+  return occ;
+}
 #endif
 
 }  // namespace fr
@@ -243,9 +307,17 @@ inline size_t cast_lds_bytes(uint32_t levels) { return (static_cast<size_t>(leve
 // Enqueues n rays (two float4 each: o, pad, d, pad) on `stream`; hit i lands in g0[i], g1[i],
 // alb[i] (the G-buffer's words). tree: walk the scene's tree (sc.n_segs > 0). waves:
 // kCastWaveBytes, zeroed by the caller; +1 per wave that walked the tree (word 0 of a stripe) /
-// fell back to the list (word 1).
+// fell back to the list (word 1). ranged: a ray's second word's .w is its t_max;
+// otherwise the word is not read and t_max is kCastTMax.
 hipError_t launch_cast(hipStream_t stream, const CastScene& sc, bool tree, const float4* rays, uint32_t n, float4* g0,
-                       float4* g1, float4* alb, uint32_t* waves);
+                       float4* g1, float4* alb, uint32_t* waves, bool ranged = false);
+// Occlusion queries (occlude.hip): out[i] = 1 if anything of the scene lies in
+// (kGbTMin, t_max_i) of ray i, else 0; t_max_i is the second word's .w if ranged, else kCastTMax.
+// waves: as launch_cast's, and word 2 of a stripe receives the wave's count of occluded rays.
+hipError_t launch_occlude(hipStream_t stream, const CastScene& sc, bool tree, const float4* rays, uint32_t n, bool ranged,
+                          uint8_t* out, uint32_t* waves);
+// cast.hip's check of the tables a launch reads.
+bool cast_scene_ok(const CastScene& sc, bool tree);
 // fr_ctx_gbuffer through the tree: launch_gbuffer's contract for a scene with segments.
 hipError_t launch_gbuffer_tree(hipStream_t stream, const CastScene& sc, const GbCam& cam, uint32_t W, uint32_t H, float4* g0,
                                float4* g1, float4* alb);

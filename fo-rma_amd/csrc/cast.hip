@@ -4,7 +4,9 @@
 // its own tree, bvh.h), and writes the winner as the G-buffer's three 16-byte words. The
 // arithmetic is cast.h's and gbuffer.h's; the tree walk equals the list loop bit for bit, and a
 // wave holding a ray the cull is not conservative for (cast_fallback) walks the list for all its
-// lanes. gbuffer_tree_kernel is the same walk with the pinhole ray of a pixel as the ray source.
+// lanes. cast_kernel<TREE, true> starts closest at the ray's own t_max (FR_CAST_TMAX, DESIGN.md
+// §4.5h) and is otherwise the same kernel. gbuffer_tree_kernel is the same walk with the pinhole
+// ray of a pixel as the ray source.
 // No scratch; no atomics but one add per wave into the cast's striped wave counter; the tree
 // walk's per-lane traversal stack is dynamic LDS, level-major (cast_lds_bytes).
 #include "cast.h"
@@ -27,10 +29,12 @@ struct CastLeafRec {  // a leaf-order record by per-lane buffer loads
 
 // The closest hit of r: closest and best as the list loop leaves them. tid: the lane's index in
 // its workgroup. Every lane of the wave must be here (the table indices are wave-uniform and
-// the fallback is a ballot). Returns true if the wave walked the list.
+// the fallback is a ballot). Returns true if the wave walked the list. t_max: what closest starts
+// at, the ray's range; the walks below are written against closest alone.
 template <bool TREE>
-__device__ __forceinline__ bool cast_walk(const CastScene& sc, const GbRay& r, uint32_t tid, float& closest, int& best) {
-  closest = kCastTMax;
+__device__ __forceinline__ bool cast_walk(const CastScene& sc, const GbRay& r, uint32_t tid, float& closest, int& best,
+                                          const float t_max = kCastTMax) {
+  closest = t_max;
   best = -1;
   typedef __attribute__((address_space(4))) const uint32_t cu32;
   bool list_walk = !TREE;
@@ -174,7 +178,8 @@ struct CastArgs {
   uint32_t* waves;
 };
 
-template <bool TREE>
+// RANGED: the ray's t_max is its second word's .w (FR_CAST_TMAX); otherwise the word is not read.
+template <bool TREE, bool RANGED = false>
 __global__ __launch_bounds__(kCastBlock) void cast_kernel(CastArgs a) {
   const uint32_t tid = threadIdx.x;
   const uint32_t i = blockIdx.x * kCastBlock + tid;
@@ -185,7 +190,7 @@ __global__ __launch_bounds__(kCastBlock) void cast_kernel(CastArgs a) {
   const GbRay r = cast_ray(V3{ro.x, ro.y, ro.z}, V3{rd.x, rd.y, rd.z});
   float closest;
   int best;
-  const bool list_walk = cast_walk<TREE>(a.sc, r, tid, closest, best);
+  const bool list_walk = cast_walk<TREE>(a.sc, r, tid, closest, best, RANGED ? rd.w : kCastTMax);
   // one add per wave that holds a ray (a wave's first lane has its lowest index)
   if ((tid & 63u) == 0u && inside)
     atomicAdd(&a.waves[(blockIdx.x % kCastStripes) * kCastStripeWords + (list_walk ? 1u : 0u)], 1u);
@@ -219,21 +224,25 @@ __global__ __launch_bounds__(kCastBlock) void gbuffer_tree_kernel(GbTreeArgs a) 
   if (inside) cast_store(a.sc.gb, r, closest, best, static_cast<size_t>(y) * a.W + x, a.g0, a.g1, a.alb);
 }
 
-static bool cast_scene_ok(const CastScene& sc, bool tree) {
+bool cast_scene_ok(const CastScene& sc, bool tree) {
   if (!sc.gb.rec || !sc.gb.runs || !sc.gb.cls || !sc.gb.att) return false;
   if (!tree) return true;
   return sc.bvh && sc.bvh_order && sc.lrec && sc.segs && sc.n_segs && sc.levels >= 1u && sc.levels <= kBvhStack;
 }
 
 hipError_t launch_cast(hipStream_t stream, const CastScene& sc, bool tree, const float4* rays, uint32_t n, float4* g0,
-                       float4* g1, float4* alb, uint32_t* waves) {
+                       float4* g1, float4* alb, uint32_t* waves, bool ranged) {
   if (!cast_scene_ok(sc, tree) || !rays || !n || !g0 || !g1 || !alb || !waves) return hipErrorInvalidValue;
   const dim3 grid((n + kCastBlock - 1u) / kCastBlock), block(kCastBlock);
   const CastArgs a{sc, rays, n, g0, g1, alb, waves};
-  if (tree)
-    hipLaunchKernelGGL(cast_kernel<true>, grid, block, cast_lds_bytes(sc.levels), stream, a);
+  if (tree && ranged)
+    hipLaunchKernelGGL((cast_kernel<true, true>), grid, block, cast_lds_bytes(sc.levels), stream, a);
+  else if (tree)
+    hipLaunchKernelGGL((cast_kernel<true, false>), grid, block, cast_lds_bytes(sc.levels), stream, a);
+  else if (ranged)
+    hipLaunchKernelGGL((cast_kernel<false, true>), grid, block, 0, stream, a);
   else
-    hipLaunchKernelGGL(cast_kernel<false>, grid, block, 0, stream, a);
+    hipLaunchKernelGGL((cast_kernel<false, false>), grid, block, 0, stream, a);
   return hipGetLastError();
 }
 

@@ -236,6 +236,14 @@ struct fr_ctx {
   uint32_t* d_cast_waves = nullptr;
   uint32_t cast_cap = 0, cast_n = 0;
   bool cast_valid = false, cast_tree = false;
+  // fr_ctx_occluded: one byte per ray and a wave counter of its own (the last
+  // cast's stays what it is), allocated on first use; the bytes are replaced when n outgrows
+  // occl_cap. occl_out: where the last query wrote (d_occl, or the caller's device buffer).
+  uint8_t* d_occl = nullptr;
+  uint32_t* d_occl_waves = nullptr;
+  const uint8_t* occl_out = nullptr;
+  uint32_t occl_cap = 0, occl_n = 0;
+  bool occl_valid = false, occl_tree = false;
   // fr_ctx_temporal. accum_gen: the accumulation generation, advanced whenever
   // accum_step starts a new accumulation. d_gb_cls: the G-buffer's scene's effective scatter
   // classes, gb_n of them, copied with every fr_ctx_gbuffer (the scene's own table dies with an
@@ -637,7 +645,8 @@ void fr_ctx_free(fr_ctx* c) {
                   static_cast<void*>(c->d_tp_tq[1]), static_cast<void*>(c->d_tp_g0), static_cast<void*>(c->d_tp_g1),
                   static_cast<void*>(c->d_tp_pa), static_cast<void*>(c->d_tp_pq), static_cast<void*>(c->d_tp_src),
                   static_cast<void*>(c->d_tp_why), static_cast<void*>(c->d_cast_rays), static_cast<void*>(c->d_hit0),
-                  static_cast<void*>(c->d_hit1), static_cast<void*>(c->d_hit_alb), static_cast<void*>(c->d_cast_waves)})
+                  static_cast<void*>(c->d_hit1), static_cast<void*>(c->d_hit_alb), static_cast<void*>(c->d_cast_waves),
+                  static_cast<void*>(c->d_occl), static_cast<void*>(c->d_occl_waves)})
     if (d) (void)hipFree(d);
   if (c->h_cast_rays) (void)hipHostFree(c->h_cast_rays);
   for (hipEvent_t e : {c->ev0, c->ev1, c->ev_start, c->ev_copy, c->ev_cast})
@@ -1412,20 +1421,49 @@ int fr_ctx_gbuffer_info(fr_ctx* c, int* tree) {
   return FR_OK;
 }
 
+// The n rays of a query on the device: the caller's device pointer, or the context's copy of the
+// caller's host rays, which leave through a pinned buffer the context owns (copied before the
+// call returns; the device copy stays asynchronous on the sum stream).
+static int stage_rays(fr_ctx* c, const fr_ray* rays, uint32_t n, bool host_rays, const float4** d_rays) {
+  *d_rays = reinterpret_cast<const float4*>(rays);
+  if (!host_rays) return FR_OK;
+  const size_t ray_bytes = static_cast<size_t>(n) * sizeof(fr_ray);
+  int rc;
+  if (!c->ev_cast) HIPCHK(hipEventCreateWithFlags(&c->ev_cast, hipEventDisableTiming));
+  if (c->cap_cast_rays < ray_bytes) {
+    HIPCHK(hipStreamSynchronize(c->stream_sum));  // an earlier query may still read the smaller copy
+    if ((rc = grow(c->d_cast_rays, c->cap_cast_rays, ray_bytes))) return rc;
+  }
+  if (c->cast_copy_pending) HIPCHK(hipEventSynchronize(c->ev_cast));
+  c->cast_copy_pending = false;
+  if (c->cap_cast_host < ray_bytes) {
+    if (c->h_cast_rays) HIPCHK(hipHostFree(c->h_cast_rays));
+    c->h_cast_rays = nullptr;
+    c->cap_cast_host = 0;
+    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&c->h_cast_rays), ray_bytes, hipHostMallocDefault));
+    c->cap_cast_host = ray_bytes;
+  }
+  memcpy(c->h_cast_rays, rays, ray_bytes);
+  HIPCHK(hipMemcpyAsync(c->d_cast_rays, c->h_cast_rays, ray_bytes, hipMemcpyHostToDevice, c->stream_sum));
+  HIPCHK(hipEventRecord(c->ev_cast, c->stream_sum));
+  c->cast_copy_pending = true;
+  *d_rays = c->d_cast_rays;
+  return FR_OK;
+}
+
 // Ray queries: one cast kernel on the sum stream, behind whatever is enqueued
 // there; nothing is waited for but the pinned staging buffer's previous copy. Frames, A, Q, the
 // outputs, the pending render and its stats, the G-buffer and the history are untouched.
 int fr_ctx_cast(fr_ctx* c, fr_scene* scene, const fr_ray* rays, uint32_t n, uint32_t flags) {
   if (!c || !scene || !rays) return set_error(FR_EARG, "fr_ctx_cast: null argument");
   if (!n || n > (1u << 27)) return set_error(FR_EARG, "fr_ctx_cast: n %u must be 1 to 2^27", n);
-  if (flags & ~(FR_CAST_LIST | FR_CAST_RAYS_DEVICE)) return set_error(FR_EARG, "fr_ctx_cast: unknown flags 0x%x", flags);
+  if (flags & ~(FR_CAST_LIST | FR_CAST_RAYS_DEVICE | FR_CAST_TMAX))
+    return set_error(FR_EARG, "fr_ctx_cast: unknown flags 0x%x", flags);
   SET_DEVICE(c->device);
   const PlanEnv env = read_plan_env();
   DeviceCopy* dc = nullptr;
   int rc;
   if ((rc = upload_scene(scene, c->device, env.bvh_force, &dc))) return rc;
-  const size_t ray_bytes = static_cast<size_t>(n) * sizeof(fr_ray);
-  const bool host_rays = !(flags & FR_CAST_RAYS_DEVICE);
   if (n > c->cast_cap || !c->d_cast_waves) {
     HIPCHK(hipStreamSynchronize(c->stream_sum));  // the kernels and copies that use the old buffers
     c->cast_valid = false;
@@ -1436,37 +1474,16 @@ int fr_ctx_cast(fr_ctx* c, fr_scene* scene, const fr_ray* rays, uint32_t n, uint
     if ((rc = grow(c->d_hit1, caps[1], bytes))) return rc;
     if ((rc = grow(c->d_hit_alb, caps[2], bytes))) return rc;
     if (!c->d_cast_waves) HIPCHK(hipMalloc(&c->d_cast_waves, kCastWaveBytes));
-    if (!c->ev_cast) HIPCHK(hipEventCreateWithFlags(&c->ev_cast, hipEventDisableTiming));
     c->cast_cap = n;
   }
-  const float4* d_rays = reinterpret_cast<const float4*>(rays);
-  if (host_rays) {
-    if (c->cap_cast_rays < ray_bytes) {
-      HIPCHK(hipStreamSynchronize(c->stream_sum));  // an earlier cast may still read the smaller copy
-      if ((rc = grow(c->d_cast_rays, c->cap_cast_rays, ray_bytes))) return rc;
-    }
-    // the caller's rays leave through a pinned buffer the context owns: copied before the
-    // call returns, and the device copy stays asynchronous
-    if (c->cast_copy_pending) HIPCHK(hipEventSynchronize(c->ev_cast));
-    c->cast_copy_pending = false;
-    if (c->cap_cast_host < ray_bytes) {
-      if (c->h_cast_rays) HIPCHK(hipHostFree(c->h_cast_rays));
-      c->h_cast_rays = nullptr;
-      c->cap_cast_host = 0;
-      HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&c->h_cast_rays), ray_bytes, hipHostMallocDefault));
-      c->cap_cast_host = ray_bytes;
-    }
-    memcpy(c->h_cast_rays, rays, ray_bytes);
-    HIPCHK(hipMemcpyAsync(c->d_cast_rays, c->h_cast_rays, ray_bytes, hipMemcpyHostToDevice, c->stream_sum));
-    HIPCHK(hipEventRecord(c->ev_cast, c->stream_sum));
-    c->cast_copy_pending = true;
-    d_rays = c->d_cast_rays;
-  }
+  const float4* d_rays = nullptr;
+  if ((rc = stage_rays(c, rays, n, !(flags & FR_CAST_RAYS_DEVICE), &d_rays))) return rc;
   const CastScene cs = cast_scene(dc);
   const bool tree = cs.n_segs > 0 && !(flags & FR_CAST_LIST);
   HIPCHK(hipMemsetAsync(c->d_cast_waves, 0, kCastWaveBytes, c->stream_sum));
   if (c->log_on) HIPCHK(log_start(c, 3, c->stream_sum));
-  HIPCHK(launch_cast(c->stream_sum, cs, tree, d_rays, n, c->d_hit0, c->d_hit1, c->d_hit_alb, c->d_cast_waves));
+  HIPCHK(launch_cast(c->stream_sum, cs, tree, d_rays, n, c->d_hit0, c->d_hit1, c->d_hit_alb, c->d_cast_waves,
+                     (flags & FR_CAST_TMAX) != 0));
   if (c->log_on) HIPCHK(log_end(c, 3, c->stream_sum));
   c->cast_n = n;
   c->cast_tree = tree;
@@ -1497,6 +1514,79 @@ int fr_ctx_cast_info(fr_ctx* c, fr_cast_info* out) {
   out->tree = c->cast_tree ? 1u : 0u;
   out->waves_tree = waves[0];
   out->waves_list = waves[1];
+  return FR_OK;
+}
+
+int fr_ctx_hit_buffers(fr_ctx* c, void** g0, void** g1, void** alb, uint32_t* n) {
+  if (!c) return set_error(FR_EARG, "fr_ctx_hit_buffers: null ctx");
+  if (!c->cast_valid) return set_error(FR_EARG, "fr_ctx_hit_buffers: no hits (fr_ctx_cast first)");
+  if (g0) *g0 = c->d_hit0;
+  if (g1) *g1 = c->d_hit1;
+  if (alb) *alb = c->d_hit_alb;
+  if (n) *n = c->cast_n;
+  return FR_OK;
+}
+
+// Occlusion queries: fr_ctx_cast's driver with one byte per ray for the hits
+// and a wave counter of its own. Frames, A, Q, the outputs, the pending render and its stats, the
+// G-buffer, the history and the last cast's hits and counter are untouched.
+int fr_ctx_occluded(fr_ctx* c, fr_scene* scene, const fr_ray* rays, uint32_t n, uint32_t flags, uint8_t* out) {
+  if (!c || !scene || !rays) return set_error(FR_EARG, "fr_ctx_occluded: null argument");
+  if (!n || n > (1u << 27)) return set_error(FR_EARG, "fr_ctx_occluded: n %u must be 1 to 2^27", n);
+  if (flags & ~(FR_CAST_LIST | FR_CAST_RAYS_DEVICE | FR_CAST_TMAX | FR_CAST_OUT_DEVICE))
+    return set_error(FR_EARG, "fr_ctx_occluded: unknown flags 0x%x", flags);
+  const bool out_device = (flags & FR_CAST_OUT_DEVICE) != 0;
+  if (out_device && !out) return set_error(FR_EARG, "fr_ctx_occluded: FR_CAST_OUT_DEVICE with a NULL out");
+  SET_DEVICE(c->device);
+  const PlanEnv env = read_plan_env();
+  DeviceCopy* dc = nullptr;
+  int rc;
+  if ((rc = upload_scene(scene, c->device, env.bvh_force, &dc))) return rc;
+  if (!c->d_occl_waves) HIPCHK(hipMalloc(&c->d_occl_waves, kCastWaveBytes));
+  if (!out_device && n > c->occl_cap) {
+    HIPCHK(hipStreamSynchronize(c->stream_sum));  // the kernels and copies that use the old bytes
+    if (c->occl_out == c->d_occl) c->occl_valid = false;
+    c->occl_cap = 0;
+    size_t cap = 0;  // (grow with no capacity: the buffer is replaced)
+    if ((rc = grow(c->d_occl, cap, n))) return rc;
+    c->occl_cap = n;
+  }
+  const float4* d_rays = nullptr;
+  if ((rc = stage_rays(c, rays, n, !(flags & FR_CAST_RAYS_DEVICE), &d_rays))) return rc;
+  const CastScene cs = cast_scene(dc);
+  const bool tree = cs.n_segs > 0 && !(flags & FR_CAST_LIST);
+  uint8_t* d_out = out_device ? out : c->d_occl;
+  HIPCHK(hipMemsetAsync(c->d_occl_waves, 0, kCastWaveBytes, c->stream_sum));
+  if (c->log_on) HIPCHK(log_start(c, 3, c->stream_sum));
+  HIPCHK(launch_occlude(c->stream_sum, cs, tree, d_rays, n, (flags & FR_CAST_TMAX) != 0, d_out, c->d_occl_waves));
+  if (c->log_on) HIPCHK(log_end(c, 3, c->stream_sum));
+  c->occl_n = n;
+  c->occl_tree = tree;
+  c->occl_out = d_out;
+  c->occl_valid = true;
+  return FR_OK;
+}
+
+int fr_ctx_download_occluded(fr_ctx* c, uint8_t* host) {
+  if (!c) return set_error(FR_EARG, "fr_ctx_download_occluded: null ctx");
+  if (!c->occl_valid) return set_error(FR_EARG, "fr_ctx_download_occluded: no query (fr_ctx_occluded first)");
+  SET_DEVICE(c->device);
+  if (host) HIPCHK(hipMemcpyAsync(host, c->occl_out, c->occl_n, hipMemcpyDeviceToHost, c->stream_sum));
+  HIPCHK(hipStreamSynchronize(c->stream_sum));
+  return FR_OK;
+}
+
+int fr_ctx_occluded_info(fr_ctx* c, fr_occl_info* out) {
+  if (!c || !out) return set_error(FR_EARG, "fr_ctx_occluded_info: null argument");
+  if (!c->occl_valid) return set_error(FR_EARG, "fr_ctx_occluded_info: no query (fr_ctx_occluded first)");
+  SET_DEVICE(c->device);
+  std::vector<uint32_t> stripes(kCastWaveBytes / 4);
+  HIPCHK(hipMemcpyAsync(stripes.data(), c->d_occl_waves, kCastWaveBytes, hipMemcpyDeviceToHost, c->stream_sum));
+  HIPCHK(hipStreamSynchronize(c->stream_sum));
+  uint32_t sum[3] = {0, 0, 0};
+  for (uint32_t k = 0; k < kCastStripes; ++k)
+    for (uint32_t j = 0; j < 3; ++j) sum[j] += stripes[k * kCastStripeWords + j];
+  *out = fr_occl_info{c->occl_n, c->occl_tree ? 1u : 0u, sum[0], sum[1], sum[2], {0, 0, 0}};
   return FR_OK;
 }
 
@@ -1827,7 +1917,7 @@ int fr_ctx_trace_log_read(fr_ctx* c, int which, double* ms, uint32_t cap, uint32
   // which 0 / 1: durations of the trace launches / renders; 2 / 3: their start and end times
   // (two values each) from the first logged trace launch's start (a timeline); 4: durations of
   // the stages of the fr_ctx_temporal calls, three entries per call; 5: durations of the cast
-  // kernels and G-buffer passes
+  // and occlusion kernels and G-buffer passes
   const int w = which == 5 ? 3 : which == 4 ? 2 : which & 1;
   *n = static_cast<uint32_t>(c->log_n[w]);
   for (size_t i = 0; i < c->log_n[w] && ms; ++i) {

@@ -133,9 +133,16 @@ class FrCastInfo(C.Structure):
     _fields_ = [("n", C.c_uint32), ("tree", C.c_uint32), ("waves_tree", C.c_uint32), ("waves_list", C.c_uint32)]
 
 
-# fr_ctx_cast flags (forma_rt.h)
+class FrOcclInfo(C.Structure):
+    _fields_ = [("n", C.c_uint32), ("tree", C.c_uint32), ("waves_tree", C.c_uint32), ("waves_list", C.c_uint32),
+                ("occluded", C.c_uint32), ("pad", C.c_uint32 * 3)]
+
+
+# fr_ctx_cast / fr_ctx_occluded flags (forma_rt.h)
 FR_CAST_LIST = 1
 FR_CAST_RAYS_DEVICE = 2
+FR_CAST_TMAX = 16  # (4 stays an unknown flag: fr_ctx_cast has refused it since it was built)
+FR_CAST_OUT_DEVICE = 8
 
 
 # Every symbol include/forma_rt.h declares (checked by tests/test_abi.py).
@@ -160,6 +167,7 @@ EXPORTS = (
     "fr_camera_axial", "fr_ctx_camera_path", "fr_selftest_camray", "fr_selftest_boxinv",
     "fr_ctx_temporal", "fr_ctx_temporal_reset", "fr_ctx_download_temporal",
     "fr_ctx_gbuffer_info", "fr_camera_pixel_ray", "fr_ctx_cast", "fr_ctx_download_hits", "fr_ctx_cast_info",
+    "fr_ctx_hit_buffers", "fr_ctx_occluded", "fr_ctx_download_occluded", "fr_ctx_occluded_info",
 )
 
 _lib = None
@@ -289,6 +297,11 @@ def lib():
         L.fr_ctx_cast.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32]
         L.fr_ctx_download_hits.argtypes = [vp, P(C.c_uint32), f3, f3, f3, f3]
         L.fr_ctx_cast_info.argtypes = [vp, P(FrCastInfo)]
+    if hasattr(L, "fr_ctx_occluded"):
+        L.fr_ctx_hit_buffers.argtypes = [vp, P(vp), P(vp), P(vp), P(C.c_uint32)]
+        L.fr_ctx_occluded.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32, vp]
+        L.fr_ctx_download_occluded.argtypes = [vp, vp]
+        L.fr_ctx_occluded_info.argtypes = [vp, P(FrOcclInfo)]
     _lib = L
     return L
 
@@ -745,31 +758,102 @@ class RenderContext:
         check(lib().fr_ctx_gbuffer_info(self._h, C.byref(t)))
         return "tree" if t.value else "list"
 
-    def cast(self, scene, origins, directions=None, list_walk=False):
-        """The closest hit of each ray (fr_ctx_cast, fr_ctx_download_hits): origins and directions
-        numpy [n, 3] f32 arrays, or origins a torch tensor [n, 8] f32 on the context's device
-        holding (o, pad, d, pad) per row, complete on the device at the call (directions None).
-        list_walk: the list in order even if the scene has a tree. Returns download_gbuffer()'s
-        dict with "t" for "depth": "prim" [n] uint32 (FR_GBUFFER_MISS for a miss), "t" [n] f32,
-        "normal", "position" and "albedo" [n, 3] f32. Waits for the hits."""
-        flags = FR_CAST_LIST if list_walk else 0
+    @staticmethod
+    def _rays(who, origins, directions, t_max):
+        """(a [n, 8] f32 array or torch tensor to keep alive, its address, n, flags) of a query's
+        rays: origins and directions numpy [n, 3] with t_max None, a scalar or an [n] array, or
+        origins a torch [n, 8] device tensor (directions None) with t_max None or True (column 7)."""
         if directions is None and hasattr(origins, "data_ptr"):
             t = origins
             if t.dim() != 2 or t.shape[1] != 8 or str(t.dtype) != "torch.float32" or not t.is_cuda or not t.is_contiguous():
-                raise ForMaError(FR_EARG, "cast: device rays must be a contiguous float32 [n, 8] tensor on the device")
-            n = int(t.shape[0])
-            check(lib().fr_ctx_cast(self._h, scene._h, C.c_void_p(t.data_ptr()), n, flags | FR_CAST_RAYS_DEVICE))
-        else:
-            o = np.ascontiguousarray(origins, dtype=np.float32)
-            d = np.ascontiguousarray(directions, dtype=np.float32)
-            if o.ndim != 2 or o.shape[1] != 3 or d.shape != o.shape:
-                raise ForMaError(FR_EARG, "cast: origins and directions must be [n, 3] arrays of one length")
-            n = int(o.shape[0])
-            rays = np.zeros((n, 8), dtype=np.float32)
-            rays[:, 0:3] = o
-            rays[:, 4:7] = d
-            check(lib().fr_ctx_cast(self._h, scene._h, rays.ctypes.data_as(C.c_void_p), n, flags))
+                raise ForMaError(FR_EARG, f"{who}: device rays must be a contiguous float32 [n, 8] tensor on the device")
+            if t_max is not None and t_max is not True and t_max is not False:
+                raise ForMaError(FR_EARG, f"{who}: t_max of device rays is True (column 7 holds it) or None")
+            return t, t.data_ptr(), int(t.shape[0]), FR_CAST_RAYS_DEVICE | (FR_CAST_TMAX if t_max else 0)
+        o = np.ascontiguousarray(origins, dtype=np.float32)
+        d = np.ascontiguousarray(directions, dtype=np.float32)
+        if o.ndim != 2 or o.shape[1] != 3 or d.shape != o.shape:
+            raise ForMaError(FR_EARG, f"{who}: origins and directions must be [n, 3] arrays of one length")
+        n = int(o.shape[0])
+        rays = np.zeros((n, 8), dtype=np.float32)
+        rays[:, 0:3] = o
+        rays[:, 4:7] = d
+        flags = 0
+        if t_max is not None:
+            tm = np.asarray(t_max, dtype=np.float32)
+            if tm.ndim > 1 or (tm.ndim == 1 and tm.shape[0] != n):
+                raise ForMaError(FR_EARG, f"{who}: t_max must be a scalar or an [n] array")
+            rays[:, 7] = tm
+            flags = FR_CAST_TMAX
+        return rays, rays.ctypes.data, n, flags
+
+    def cast(self, scene, origins, directions=None, list_walk=False, t_max=None):
+        """The closest hit of each ray (fr_ctx_cast, fr_ctx_download_hits): origins and directions
+        numpy [n, 3] f32 arrays, or origins a torch tensor [n, 8] f32 on the context's device
+        holding (o, pad, d, pad) per row, complete on the device at the call (directions None).
+        list_walk: the list in order even if the scene has a tree. t_max: each ray's range
+        (FR_CAST_TMAX), a scalar or an [n] array; for a device tensor True, and column 7 holds it.
+        None: FLT_MAX, and the pad is ignored. Returns download_gbuffer()'s
+        dict with "t" for "depth": "prim" [n] uint32 (FR_GBUFFER_MISS for a miss), "t" [n] f32,
+        "normal", "position" and "albedo" [n, 3] f32. Waits for the hits."""
+        keep, addr, n, flags = self._rays("cast", origins, directions, t_max)
+        check(lib().fr_ctx_cast(self._h, scene._h, C.c_void_p(addr), n, flags | (FR_CAST_LIST if list_walk else 0)))
+        del keep
         return self.download_hits(n)
+
+    def occluded(self, scene, origins, directions=None, t_max=None, list_walk=False, out=None):
+        """Whether anything of the scene lies within (0.001, t_max) of each ray (fr_ctx_occluded):
+        rays and t_max as cast()'s. Returns an [n] bool numpy array, or, with out a contiguous
+        torch.uint8 [n] tensor on the context's device, fills it with 0 / 1 on the device, waits and
+        returns it."""
+        keep, addr, n, flags = self._rays("occluded", origins, directions, t_max)
+        flags |= FR_CAST_LIST if list_walk else 0
+        if out is not None:
+            if (not hasattr(out, "data_ptr") or out.dim() != 1 or out.shape[0] != n or str(out.dtype) != "torch.uint8"
+                    or not out.is_cuda or not out.is_contiguous()):
+                raise ForMaError(FR_EARG, "occluded: out must be a contiguous uint8 [n] tensor on the device")
+            check(lib().fr_ctx_occluded(self._h, scene._h, C.c_void_p(addr), n, flags | FR_CAST_OUT_DEVICE,
+                                        C.c_void_p(out.data_ptr())))
+            check(lib().fr_ctx_download_occluded(self._h, None))  # the wait
+            del keep
+            return out
+        check(lib().fr_ctx_occluded(self._h, scene._h, C.c_void_p(addr), n, flags, None))
+        del keep
+        return self.download_occluded(n)
+
+    def visible(self, scene, a, b):
+        """[n] bool: nothing of the scene lies between the points a and b ([n, 3] each):
+        ~occluded() of the rays o = a, d = b - a (in f32) with t_max = 1."""
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        b = np.ascontiguousarray(b, dtype=np.float32)
+        with np.errstate(all="ignore"):
+            d = (b - a).astype(np.float32)
+        return ~self.occluded(scene, a, d, t_max=1.0)
+
+    def download_occluded(self, n):
+        """The last occluded()'s n answers as an [n] bool array. Waits for them."""
+        i = FrOcclInfo()
+        check(lib().fr_ctx_occluded_info(self._h, C.byref(i)))
+        if n != i.n:
+            raise ForMaError(FR_EARG, f"download_occluded: the last query had {i.n} rays, not {n}")
+        got = np.zeros(n, dtype=np.uint8)
+        check(lib().fr_ctx_download_occluded(self._h, got.ctypes.data_as(C.c_void_p)))
+        return got != 0
+
+    def occluded_info(self):
+        """The last occluded() as a dict: cast_info()'s fields and "occluded", the number of
+        occluded rays counted on the device. Waits for it."""
+        i = FrOcclInfo()
+        check(lib().fr_ctx_occluded_info(self._h, C.byref(i)))
+        return {"n": i.n, "tree": i.tree, "waves_tree": i.waves_tree, "waves_list": i.waves_list, "occluded": i.occluded}
+
+    def hit_buffers(self):
+        """(g0, g1, alb, n): the device addresses of the last cast()'s hits, three arrays of n
+        16-byte words (normal xyz, t), (position xyz, prim bits), (albedo rgb, 0), and n
+        (fr_ctx_hit_buffers). Waits for nothing: sync through cast_info() or download_hits()."""
+        g0, g1, alb, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint32(0)
+        check(lib().fr_ctx_hit_buffers(self._h, C.byref(g0), C.byref(g1), C.byref(alb), C.byref(n)))
+        return g0.value, g1.value, alb.value, n.value
 
     def download_hits(self, n):
         """The last cast()'s n hits as cast() returns them. Waits for them."""

@@ -68,6 +68,8 @@ extern "C" {
                                fr_ctx_temporal, fr_ctx_temporal_reset, fr_ctx_download_temporal) */
 /* (still 6, additive too: fr_ray, fr_cast_info, fr_camera_pixel_ray, fr_ctx_cast, fr_ctx_download_hits,
    fr_ctx_cast_info, fr_ctx_gbuffer_info; fr_ctx_trace_log_read which = 5) */
+/* (still 6, additive too: FR_CAST_TMAX, FR_CAST_OUT_DEVICE, fr_occl_info, fr_ctx_occluded,
+   fr_ctx_download_occluded, fr_ctx_occluded_info, fr_ctx_hit_buffers) */
 
 /* error codes */
 #define FR_OK 0
@@ -310,9 +312,9 @@ int fr_ctx_device_buffers(fr_ctx* ctx, float** d_mean_rgb, uint8_t** d_rgb8);
    start (2 values per entry, a timeline); which = 4 the stages of every fr_ctx_temporal call,
    three entries per call in order: the prior (reprojection and the copy of the view's G-buffer
    words, or the fills of an empty prior; nothing when the prior is kept), totals and prep, the
-   picture (the levels, or the finalise kernel); which = 5 every cast kernel (fr_ctx_cast) and
-   G-buffer pass (fr_ctx_gbuffer) enqueued while the log is on; *n = the entries logged. Lets a caller
-   streaming K frames average all K of them and see the gaps between them. */
+   picture (the levels, or the finalise kernel); which = 5 every cast kernel (fr_ctx_cast),
+   occlusion kernel (fr_ctx_occluded) and G-buffer pass (fr_ctx_gbuffer) enqueued while the log is
+   on; *n = the entries logged. Lets a caller streaming K frames average all K of them and see the gaps between them. */
 int fr_ctx_trace_log(fr_ctx* ctx, int enable);
 int fr_ctx_trace_log_read(fr_ctx* ctx, int which, double* ms, uint32_t cap, uint32_t* n);
 /* Everything a render of these parameters sets up before its first launch, without
@@ -475,11 +477,18 @@ int fr_ctx_gbuffer_info(fr_ctx* ctx, int* tree);
    accumulation, the outputs, the pending render and its stats, the G-buffer and the temporal
    history are untouched. FR_EARG, with nothing enqueued, for n = 0, n > 2^27, a NULL pointer or an
    unknown flag. */
-typedef struct fr_ray { float o[3]; float pad0; float d[3]; float pad1; } fr_ray;      /* 32 bytes; pads ignored */
+typedef struct fr_ray { float o[3]; float pad0; float d[3]; float pad1; } fr_ray;      /* 32 bytes; pads ignored (pad1: FR_CAST_TMAX) */
 typedef struct fr_cast_info { uint32_t n, tree, waves_tree, waves_list; } fr_cast_info; /* tree: 1 if the scene's tree was walked */
 #define FR_CAST_LIST        1u   /* walk the list in order even if the scene has a tree */
 #define FR_CAST_RAYS_DEVICE 2u   /* rays is a device pointer on the context's device, complete at the call,
                                     valid until fr_ctx_download_hits returns */
+#define FR_CAST_TMAX 16u         /* fr_ray::pad1 is the ray's t_max: closest starts at it instead of FLT_MAX
+                                    and nothing else changes, so the hit is the list loop's over (0.001,
+                                    t_max), planes gated on their denominator against closest as ever;
+                                    whatever NaN (a miss), +-inf, 0 or a negative gives in the loop's
+                                    comparisons is the answer. Without it the pad is ignored */
+#define FR_CAST_OUT_DEVICE 8u    /* fr_ctx_occluded only: out is a device pointer of n bytes on the context's
+                                    device, written by the kernel, valid until the query has completed */
 /* The pinhole ray of pixel (x, y) of a W x H view, fr_ctx_gbuffer's: o = position,
    d = ((lower_left + u horizontal) + v vertical) - position. Host only. FR_EARG for a NULL
    pointer, W or H of 0, x >= W or y >= H. */
@@ -493,6 +502,39 @@ int fr_ctx_download_hits(fr_ctx* ctx, uint32_t* prim, float* t, float* normal, f
    reach or is NaN, whose direction is below 2^-60 in every component, or whose o / d overflows,
    walks the list for all its rays); the two sum to ceil(n / 64). */
 int fr_ctx_cast_info(fr_ctx* ctx, fr_cast_info* out);   /* waits, like the download */
+/* The device addresses of the last fr_ctx_cast's hits, left on the device: three arrays of *n
+   16-byte words, g0 = (normal xyz, t), g1 = (position xyz, the bits of prim), alb = (albedo rgb, 0),
+   on the context's device, valid until the next fr_ctx_cast of a larger n or fr_ctx_free. Any
+   pointer may be NULL. Nothing is waited for: the words are complete after fr_ctx_sync,
+   fr_ctx_cast_info or fr_ctx_download_hits. FR_EARG if nothing was cast. */
+int fr_ctx_hit_buffers(fr_ctx* ctx, void** g0, void** g1, void** alb, uint32_t* n);
+
+/* Occlusion queries (any hit): out[i] = 1 if a primitive of the scene is hit by ray i within
+   (0.001, t_max_i), else 0; t_max_i is fr_ray::pad1 with FR_CAST_TMAX, else FLT_MAX. The answer is
+   the OR over every primitive of the list of its own test against t_max_i, with the arithmetic
+   of fr_ctx_cast, and equals "fr_ctx_cast with FR_CAST_TMAX finds a hit" on every ray, t_max of
+   NaN (never occluded), infinities, 0 and negatives included. Which primitive occludes is not
+   reported. A scene that has a tree is walked through it, each ray stopping at its first hit;
+   FR_CAST_LIST tests the list all the same. Flags: FR_CAST_LIST | FR_CAST_RAYS_DEVICE |
+   FR_CAST_TMAX | FR_CAST_OUT_DEVICE. Without FR_CAST_OUT_DEVICE the bytes stay in a buffer the
+   context owns (it grows with n) until fr_ctx_download_occluded fetches them, and out is not used
+   and may be NULL.
+   fr_ctx_occluded has fr_ctx_cast's shape: it uploads or reuses the scene's device copy, copies
+   host rays before it returns, enqueues one kernel behind the context's enqueued resolves and
+   returns at once. Frames, the accumulation, the outputs, the pending render and its stats, the
+   G-buffer, the temporal history and the last fr_ctx_cast's hits and info are untouched. FR_EARG,
+   with nothing enqueued, for n = 0, n > 2^27, a NULL ctx, scene or rays, an unknown flag, or
+   FR_CAST_OUT_DEVICE with a NULL out. */
+typedef struct fr_occl_info { uint32_t n, tree, waves_tree, waves_list, occluded, pad[3]; } fr_occl_info; /* 32 bytes */
+int fr_ctx_occluded(fr_ctx* ctx, fr_scene* scene, const fr_ray* rays, uint32_t n, uint32_t flags, uint8_t* out);
+/* Waits for the last fr_ctx_occluded, then copies its n bytes to host (NULL: only waits). After a
+   FR_CAST_OUT_DEVICE query the bytes are read from the caller's buffer, which must still be there.
+   FR_EARG if nothing was queried. */
+int fr_ctx_download_occluded(fr_ctx* ctx, uint8_t* host);
+/* The last fr_ctx_occluded: its n, whether the tree was walked, the waves (64 rays) that walked
+   the tree and that fell back to the list (fr_ctx_cast_info's rule; the two sum to ceil(n / 64))
+   and the number of occluded rays, counted on the device. Waits, like the download. */
+int fr_ctx_occluded_info(fr_ctx* ctx, fr_occl_info* out);
 
 /* Feature-guided denoise of the live accumulation: fr_ctx_denoise's a-trous filter with every
    non-centre tap's weight extended by the G-buffer of the same view.
