@@ -1,172 +1,13 @@
-// cast.hip — ray queries on the device (fr_ctx_cast): one thread per ray walks
-// the scene's list in order (TREE = false: gbuffer_kernel's loop, wave-uniform index, scalar
-// record loads) or the scene's tree (TREE = true: the list cut at its planes, each run through
-// its own tree, bvh.h), and writes the winner as the G-buffer's three 16-byte words. The
-// arithmetic is cast.h's and gbuffer.h's; the tree walk equals the list loop bit for bit, and a
-// wave holding a ray the cull is not conservative for (cast_fallback) walks the list for all its
-// lanes. cast_kernel<TREE, true> starts closest at the ray's own t_max (FR_CAST_TMAX, DESIGN.md
-// §4.5h) and is otherwise the same kernel. gbuffer_tree_kernel is the same walk with the pinhole
-// ray of a pixel as the ray source.
-// No scratch; no atomics but one add per wave into the cast's striped wave counter; the tree
-// walk's per-lane traversal stack is dynamic LDS, level-major (cast_lds_bytes).
-#include "cast.h"
-
-#include <type_traits>
-
-#include "trace_kernel.h"  // RecRef, rec_at, buf_load4, lds_u32_at: table reads as the trace kernel's
+// cast.hip — ray queries on the device (fr_ctx_cast): one thread per ray takes
+// the closest hit of scene_walk (scene_walk.h: the scene's list, or its tree with TREE = true)
+// and writes the winner as the G-buffer's three 16-byte words. cast_kernel<TREE, true> starts
+// closest at the ray's own t_max (FR_CAST_TMAX) and is otherwise the same kernel.
+// gbuffer_tree_kernel is the same walk with the pinhole ray of a pixel as the ray source.
+// No scratch; no atomics but one add per wave into the cast's striped wave counter; dynamic LDS
+// is the tree walk's stack (cast_lds_bytes).
+#include "scene_walk.h"
 
 namespace fr {
-
-extern __shared__ uint32_t cast_stack[];  // [level][lane of the workgroup]; level 0 is the sentinel row
-
-constexpr uint32_t kCastLevelB = kCastBlock * 4u;  // bytes of one stack level
-
-struct CastLeafRec {  // a leaf-order record by per-lane buffer loads
-  const float4* base;
-  uint32_t off;
-  __device__ __forceinline__ float4 operator[](uint32_t k) const { return buf_load4(base, off + 16u * k); }
-};
-
-// The closest hit of r: closest and best as the list loop leaves them. tid: the lane's index in
-// its workgroup. Every lane of the wave must be here (the table indices are wave-uniform and
-// the fallback is a ballot). Returns true if the wave walked the list. t_max: what closest starts
-// at, the ray's range; the walks below are written against closest alone.
-template <bool TREE>
-__device__ __forceinline__ bool cast_walk(const CastScene& sc, const GbRay& r, uint32_t tid, float& closest, int& best,
-                                          const float t_max = kCastTMax) {
-  closest = t_max;
-  best = -1;
-  typedef __attribute__((address_space(4))) const uint32_t cu32;
-  bool list_walk = !TREE;
-  if (TREE) {
-    const CastCull cull = cast_cull(r);
-    list_walk = __ballot(cast_fallback(r, cull, sc.reach)) != 0;
-    if (!list_walk) {
-      const uint32_t tbase = lds_addr(cast_stack) + 4u * tid;
-      lds_u32_at(tbase) = kBvhEnd;  // the sentinel: what an empty stack pops
-      for (uint32_t sg = 0; sg < sc.n_segs; ++sg) {
-        const cu32* sp = (cu32*)(reinterpret_cast<uintptr_t>(sc.segs)) + 4u * __builtin_amdgcn_readfirstlane(sg);
-        if (sp[0]) {  // a plane, where it stands
-          const uint32_t i = sp[3];
-          float t = 0.0f;
-          if (gb_test<FR_PLANE>(rec_at(sc.gb.rec, i), r, closest, t)) {
-            closest = t;
-            best = static_cast<int>(i);
-          }
-          continue;
-        }
-        uint32_t ref = sp[1];
-        uint32_t tso = tbase + kCastLevelB;  // the lane's next free entry (LDS byte address)
-        while (ref != kBvhEnd) {
-          while (ref < kBvhLeaf) {
-            // the stack's top, read before the node arrives (the sentinel when it is empty)
-            const uint32_t tdown = tso - kCastLevelB;
-            const uint32_t top = lds_u32_at(tdown);
-            CastStep st;
-            const uint32_t ref0 = __builtin_amdgcn_readfirstlane(ref);
-            if (__ballot(ref != ref0) == 0) {
-              // every walking lane at one node: scalar loads, the slabs on SGPR operands
-              const RecRef nd = rec_at(sc.bvh, ref0);
-              const float4 cr = nd[3];
-              st = cast_node_step(nd[0], nd[1], nd[2], __float_as_uint(cr.x), __float_as_uint(cr.y), cull, closest);
-              asm volatile("; cast node step: scalar");
-            } else {
-              const uint32_t nb0 = ref * 64u;  // node byte offset (< 2^32: nodes < 2^26)
-              const uint4 nr = __builtin_bit_cast(uint4, buf_load4(sc.bvh, nb0 + 48u));
-              st = cast_node_step(buf_load4(sc.bvh, nb0), buf_load4(sc.bvh, nb0 + 16u), buf_load4(sc.bvh, nb0 + 32u), nr.x,
-                                  nr.y, cull, closest);
-              asm volatile("; cast node step: vector");
-            }
-            // branch-free: the far child goes to the free entry either way (a node at depth d
-            // has at most d entries below it, d < levels) and the position moves on a push or pop
-            lds_u32_at(tso) = st.far;
-            ref = st.any ? st.near : top;
-            tso = st.both ? tso + kCastLevelB : (st.any ? tso : tdown);
-          }
-          if (ref == kBvhEnd) break;
-          // leaf: slots [first, first + count) of the leaf-order records
-          auto leaf_test = [&](const uint32_t i, const auto& lr) {
-            float t = 0.0f;
-            if (cast_leaf_test(__float_as_uint(lr[3].w), lr, r, cast_leaf_tmax(i, best, closest), t)) {
-              closest = t;
-              best = static_cast<int>(i);
-            }
-          };
-          const uint32_t leaf0 = __builtin_amdgcn_readfirstlane(ref);
-          if (__ballot(ref != leaf0) == 0) {
-            // every lane at one leaf: its records through scalar loads
-            const cu32* ord = (cu32*)(reinterpret_cast<uintptr_t>(sc.bvh_order));
-            const uint32_t first0 = leaf0 & ((1u << kBvhSlotBits) - 1u);
-            const uint32_t cnt0 = ((leaf0 >> kBvhSlotBits) & 15u) + 1u;
-            for (uint32_t kk = 0; kk < cnt0; ++kk) leaf_test(ord[first0 + kk], rec_at(sc.lrec, first0 + kk));
-            asm volatile("; cast leaf: scalar");
-          } else {
-            const uint32_t first = ref & ((1u << kBvhSlotBits) - 1u);
-            const uint32_t cnt = ((ref >> kBvhSlotBits) & 15u) + 1u;
-            for (uint32_t kk = 0; kk < cnt; ++kk) {
-              const uint32_t slot = first + kk;  // buffer loads: 32-bit offsets (slots < 2^26)
-              leaf_test(buf_load1(sc.bvh_order, slot * 4u), CastLeafRec{sc.lrec, slot * 64u});
-            }
-            asm volatile("; cast leaf: vector");
-          }
-          tso -= kCastLevelB;  // pop (the sentinel when the stack was empty)
-          ref = lds_u32_at(tso);
-        }
-      }
-    }
-  }
-  if (list_walk) {
-    auto test_one = [&](auto kind_tag, uint32_t i) {
-      float t = 0.0f;
-      if (gb_test<decltype(kind_tag)::value>(rec_at(sc.gb.rec, i), r, closest, t)) {
-        closest = t;
-        best = static_cast<int>(i);
-      }
-    };
-    // The list in order, as its kind runs: one scalar kind branch per run (gbuffer_kernel's loop).
-    for (uint32_t rr = 0; rr < sc.gb.n_runs; ++rr) {
-      const cu32* rp = (cu32*)(reinterpret_cast<uintptr_t>(sc.gb.runs)) + 4u * __builtin_amdgcn_readfirstlane(rr);
-      const uint32_t k = rp[0], i0 = rp[1], i1 = rp[2];
-      if (k == FR_AABB) {
-        for (uint32_t i = i0; i < i1; ++i)
-          test_one(std::integral_constant<uint32_t, FR_AABB>{}, __builtin_amdgcn_readfirstlane(i));
-      } else if (k == FR_SPHERE) {
-        for (uint32_t i = i0; i < i1; ++i)
-          test_one(std::integral_constant<uint32_t, FR_SPHERE>{}, __builtin_amdgcn_readfirstlane(i));
-      } else if (k == FR_PLANE) {
-        for (uint32_t i = i0; i < i1; ++i)
-          test_one(std::integral_constant<uint32_t, FR_PLANE>{}, __builtin_amdgcn_readfirstlane(i));
-      } else if (k == FR_TRIANGLE) {
-        for (uint32_t i = i0; i < i1; ++i)
-          test_one(std::integral_constant<uint32_t, FR_TRIANGLE>{}, __builtin_amdgcn_readfirstlane(i));
-      } else if (k == FR_OBB) {
-        for (uint32_t i = i0; i < i1; ++i)
-          test_one(std::integral_constant<uint32_t, FR_OBB>{}, __builtin_amdgcn_readfirstlane(i));
-      }  // FR_STUB: never hits
-    }
-  }
-  return list_walk;
-}
-
-// The winner's words at index i of the three buffers: per-lane loads of its record, class and
-// attenuation, once per ray.
-__device__ __forceinline__ void cast_store(const GbScene& sc, const GbRay& r, float closest, int best, size_t i, float4* g0,
-                                           float4* g1, float4* alb) {
-  GbPixel p = gb_miss();
-  if (best >= 0) {
-    const uint32_t b = static_cast<uint32_t>(best);
-    struct Rec {
-      float4 v[4];
-      __device__ __forceinline__ float4 operator[](int k) const { return v[k]; }
-    };
-    const float4* rb = sc.rec + 4u * static_cast<size_t>(b);
-    const Rec rec{{rb[0], rb[1], rb[2], rb[3]}};
-    p = gb_hit(b, __float_as_uint(rec.v[3].w), sc.cls[b], rec, sc.att[b], r, closest);
-  }
-  g0[i] = make_float4(p.g0.x, p.g0.y, p.g0.z, p.g0.w);
-  g1[i] = make_float4(p.g1.x, p.g1.y, p.g1.z, p.g1.w);
-  alb[i] = make_float4(p.alb.x, p.alb.y, p.alb.z, p.alb.w);
-}
 
 struct CastArgs {
   CastScene sc;
@@ -188,13 +29,12 @@ __global__ __launch_bounds__(kCastBlock) void cast_kernel(CastArgs a) {
   const size_t q = 2u * static_cast<size_t>(inside ? i : a.n - 1u);
   const float4 ro = a.rays[q], rd = a.rays[q + 1u];
   const GbRay r = cast_ray(V3{ro.x, ro.y, ro.z}, V3{rd.x, rd.y, rd.z});
-  float closest;
-  int best;
-  const bool list_walk = cast_walk<TREE>(a.sc, r, tid, closest, best, RANGED ? rd.w : kCastTMax);
+  ClosestHit h(RANGED ? rd.w : kCastTMax);
+  const bool list_walk = scene_walk<TREE>(a.sc, r, tid, h);
   // one add per wave that holds a ray (a wave's first lane has its lowest index)
   if ((tid & 63u) == 0u && inside)
     atomicAdd(&a.waves[(blockIdx.x % kCastStripes) * kCastStripeWords + (list_walk ? 1u : 0u)], 1u);
-  if (inside) cast_store(a.sc.gb, r, closest, best, i, a.g0, a.g1, a.alb);
+  if (inside) cast_store(a.sc.gb, r, h, i, a.g0, a.g1, a.alb);
 }
 
 struct GbTreeArgs {
@@ -218,10 +58,9 @@ __global__ __launch_bounds__(kCastBlock) void gbuffer_tree_kernel(GbTreeArgs a) 
   // column, and store nothing
   const bool inside = (x < a.W) & (y < a.H);
   const GbRay r = gb_primary_ray(a.cam, x < a.W ? x : a.W - 1u, y < a.H ? y : a.H - 1u, a.W, a.H);
-  float closest;
-  int best;
-  cast_walk<true>(a.sc, r, tid, closest, best);
-  if (inside) cast_store(a.sc.gb, r, closest, best, static_cast<size_t>(y) * a.W + x, a.g0, a.g1, a.alb);
+  ClosestHit h;
+  scene_walk<true>(a.sc, r, tid, h);
+  if (inside) cast_store(a.sc.gb, r, h, static_cast<size_t>(y) * a.W + x, a.g0, a.g1, a.alb);
 }
 
 bool cast_scene_ok(const CastScene& sc, bool tree) {

@@ -1,15 +1,10 @@
 // gbuffer.hip — the first-hit feature buffers on the device (fr_ctx_gbuffer):
-// one thread per pixel casts the pinhole primary ray through the scene's list, in list order,
-// and writes the winner's normal, root, point, index and attenuation as three 16-byte stores.
-// The arithmetic is gbuffer.h's. The primitive index is wave-uniform, so every record arrives
-// by scalar loads as in the trace kernel's list loop (rec_at). Scenes that have a tree take
-// gbuffer_tree_kernel (cast.hip) from a camera within the tree's reach; this
-// kernel is the pass for every other scene and camera. No atomics, no scratch, no LDS.
-#include "gbuffer.h"
-
-#include <type_traits>
-
-#include "trace_kernel.h"  // RecRef, rec_at: a record through the constant address space
+// one thread per pixel casts the pinhole primary ray through the scene's list, in list order
+// (scene_walk<false>, scene_walk.h: a wave-uniform index, scalar record loads), and writes the
+// winner's normal, root, point, index and attenuation as three 16-byte stores. Scenes that have
+// a tree take gbuffer_tree_kernel (cast.hip) from a camera within the tree's
+// reach; this kernel is the pass for every other scene and camera. No atomics, no scratch, no LDS.
+#include "scene_walk.h"
 
 namespace fr {
 
@@ -29,54 +24,9 @@ __global__ __launch_bounds__(kGbTileW* kGbTileH) void gbuffer_kernel(GbArgs a) {
   // ray of the last pixel of their row or column, and store nothing
   const bool inside = (x < a.W) & (y < a.H);
   const GbRay r = gb_primary_ray(a.cam, x < a.W ? x : a.W - 1u, y < a.H ? y : a.H - 1u, a.W, a.H);
-  float closest = 3.40282347e+38f;
-  int best = -1;
-  auto test_one = [&](auto kind_tag, uint32_t i) {
-    float t = 0.0f;
-    if (gb_test<decltype(kind_tag)::value>(rec_at(a.sc.rec, i), r, closest, t)) {
-      closest = t;
-      best = static_cast<int>(i);
-    }
-  };
-  // The list in order, as its kind runs (KScene::runs): one scalar kind branch per run.
-  typedef __attribute__((address_space(4))) const uint32_t cu32;
-  for (uint32_t rr = 0; rr < a.sc.n_runs; ++rr) {
-    const cu32* rp = (cu32*)(reinterpret_cast<uintptr_t>(a.sc.runs)) + 4u * __builtin_amdgcn_readfirstlane(rr);
-    const uint32_t k = rp[0], i0 = rp[1], i1 = rp[2];
-    if (k == FR_AABB) {
-      for (uint32_t i = i0; i < i1; ++i)
-        test_one(std::integral_constant<uint32_t, FR_AABB>{}, __builtin_amdgcn_readfirstlane(i));
-    } else if (k == FR_SPHERE) {
-      for (uint32_t i = i0; i < i1; ++i)
-        test_one(std::integral_constant<uint32_t, FR_SPHERE>{}, __builtin_amdgcn_readfirstlane(i));
-    } else if (k == FR_PLANE) {
-      for (uint32_t i = i0; i < i1; ++i)
-        test_one(std::integral_constant<uint32_t, FR_PLANE>{}, __builtin_amdgcn_readfirstlane(i));
-    } else if (k == FR_TRIANGLE) {
-      for (uint32_t i = i0; i < i1; ++i)
-        test_one(std::integral_constant<uint32_t, FR_TRIANGLE>{}, __builtin_amdgcn_readfirstlane(i));
-    } else if (k == FR_OBB) {
-      for (uint32_t i = i0; i < i1; ++i)
-        test_one(std::integral_constant<uint32_t, FR_OBB>{}, __builtin_amdgcn_readfirstlane(i));
-    }  // FR_STUB: never hits
-  }
-  if (!inside) return;
-  GbPixel p = gb_miss();
-  if (best >= 0) {
-    // the winner's record, class and attenuation: per-lane loads, once per pixel
-    const uint32_t b = static_cast<uint32_t>(best);
-    struct Rec {
-      float4 v[4];
-      __device__ __forceinline__ float4 operator[](int k) const { return v[k]; }
-    };
-    const float4* rb = a.sc.rec + 4u * static_cast<size_t>(b);
-    const Rec rec{{rb[0], rb[1], rb[2], rb[3]}};
-    p = gb_hit(b, __float_as_uint(rec.v[3].w), a.sc.cls[b], rec, a.sc.att[b], r, closest);
-  }
-  const size_t i = static_cast<size_t>(y) * a.W + x;
-  a.g0[i] = make_float4(p.g0.x, p.g0.y, p.g0.z, p.g0.w);
-  a.g1[i] = make_float4(p.g1.x, p.g1.y, p.g1.z, p.g1.w);
-  a.alb[i] = make_float4(p.alb.x, p.alb.y, p.alb.z, p.alb.w);
+  ClosestHit h;
+  scene_walk<false>(CastScene{a.sc}, r, 0u, h);  // the list alone: no other table is read
+  if (inside) cast_store(a.sc, r, h, static_cast<size_t>(y) * a.W + x, a.g0, a.g1, a.alb);
 }
 
 hipError_t launch_gbuffer(hipStream_t stream, const GbScene& sc, const GbCam& cam, uint32_t W, uint32_t H, float4* g0,

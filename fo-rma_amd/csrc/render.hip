@@ -1498,18 +1498,25 @@ int fr_ctx_download_hits(fr_ctx* c, uint32_t* prim, float* t, float* normal, flo
   return download_words(c, c->cast_n, c->d_hit0, c->d_hit1, c->d_hit_alb, prim, t, normal, position, albedo);
 }
 
+// Waits for stream_sum and sums the first k words of every stripe of a striped wave counter
+// (cast.h kCastStripes) into sum[0..k).
+static int sum_stripes(fr_ctx* c, const uint32_t* d_waves, uint32_t k, uint32_t* sum) {
+  std::vector<uint32_t> stripes(kCastWaveBytes / 4);
+  HIPCHK(hipMemcpyAsync(stripes.data(), d_waves, kCastWaveBytes, hipMemcpyDeviceToHost, c->stream_sum));
+  HIPCHK(hipStreamSynchronize(c->stream_sum));
+  for (uint32_t j = 0; j < k; ++j) sum[j] = 0;
+  for (uint32_t s = 0; s < kCastStripes; ++s)
+    for (uint32_t j = 0; j < k; ++j) sum[j] += stripes[s * kCastStripeWords + j];
+  return FR_OK;
+}
+
 int fr_ctx_cast_info(fr_ctx* c, fr_cast_info* out) {
   if (!c || !out) return set_error(FR_EARG, "fr_ctx_cast_info: null argument");
   if (!c->cast_valid) return set_error(FR_EARG, "fr_ctx_cast_info: no hits (fr_ctx_cast first)");
   SET_DEVICE(c->device);
-  std::vector<uint32_t> stripes(kCastWaveBytes / 4);
-  HIPCHK(hipMemcpyAsync(stripes.data(), c->d_cast_waves, kCastWaveBytes, hipMemcpyDeviceToHost, c->stream_sum));
-  HIPCHK(hipStreamSynchronize(c->stream_sum));
-  uint32_t waves[2] = {0, 0};
-  for (uint32_t k = 0; k < kCastStripes; ++k) {
-    waves[0] += stripes[k * kCastStripeWords];
-    waves[1] += stripes[k * kCastStripeWords + 1];
-  }
+  uint32_t waves[2];
+  int rc;
+  if ((rc = sum_stripes(c, c->d_cast_waves, 2, waves))) return rc;
   out->n = c->cast_n;
   out->tree = c->cast_tree ? 1u : 0u;
   out->waves_tree = waves[0];
@@ -1580,12 +1587,9 @@ int fr_ctx_occluded_info(fr_ctx* c, fr_occl_info* out) {
   if (!c || !out) return set_error(FR_EARG, "fr_ctx_occluded_info: null argument");
   if (!c->occl_valid) return set_error(FR_EARG, "fr_ctx_occluded_info: no query (fr_ctx_occluded first)");
   SET_DEVICE(c->device);
-  std::vector<uint32_t> stripes(kCastWaveBytes / 4);
-  HIPCHK(hipMemcpyAsync(stripes.data(), c->d_occl_waves, kCastWaveBytes, hipMemcpyDeviceToHost, c->stream_sum));
-  HIPCHK(hipStreamSynchronize(c->stream_sum));
-  uint32_t sum[3] = {0, 0, 0};
-  for (uint32_t k = 0; k < kCastStripes; ++k)
-    for (uint32_t j = 0; j < 3; ++j) sum[j] += stripes[k * kCastStripeWords + j];
+  uint32_t sum[3];
+  int rc;
+  if ((rc = sum_stripes(c, c->d_occl_waves, 3, sum))) return rc;
   *out = fr_occl_info{c->occl_n, c->occl_tree ? 1u : 0u, sum[0], sum[1], sum[2], {0, 0, 0}};
   return FR_OK;
 }

@@ -71,15 +71,7 @@
 #define FR_SUM_UNROLL 2
 #endif
 
-// occlude_kernel's tree walk (occlude.hip): 1 descends into the nearer entered child first, as
-// the cast does; 0 into the left one (the answer is an OR: any order gives it). Left first, by
-// the cast's median of the same run: 1080p on 10,000 spheres, pixel rays 0.0599 against 0.0614 ms,
-// bounce rays 0.318 against 0.335 ms, bounce rays with t_max 5 0.0508 against 0.0655 ms
-// (profiles/occlude_1080p_ab.json)
-#ifndef FR_OCCL_NEAR_FIRST
-#define FR_OCCL_NEAR_FIRST 0
-#endif
-// occlude_kernel's list loop: primitives tested between two ballots that ask whether any lane of
+// occlude_kernel's list loop (scene_walk.h AnyHit): primitives tested between two ballots that ask whether any lane of
 // the wave is still unoccluded. 10,000 spheres through the list at 1080p, pixel rays / short
 // bounce rays: 1: 8.07 / 5.39 ms, 8: 6.63 / 4.51 ms, 16: 6.25 / 4.25 ms, 64: 6.00 / 4.14 ms,
 // 256: 6.15 / 4.11 ms
@@ -101,5 +93,4 @@
   X(FR_BVH_WAVES)       \
   X(FR_MIN_WAVES)       \
   X(FR_SUM_UNROLL)      \
-  X(FR_OCCL_NEAR_FIRST) \
   X(FR_OCCL_EXIT_EVERY)

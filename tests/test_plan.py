@@ -252,7 +252,7 @@ RETIRED = ("FR_STAGE_SMAJOR FR_BVH_RSTAGE FR_TRACE_PRIO FR_CAM_RESIDENT FR_SPHER
            "FR_BVH_SCALAR_NODES FR_BVH_SCALAR_LEAVES FR_JIT_PIN FR_JIT_GROUP FR_SKY_DEFER FR_STAGE FR_BLOCK_SAMPLES "
            "FR_FINE_SAMPLES FR_SUM_UNROLL_SKYD FR_SKY_SUM_IEEE FR_XOSHIRO_PLAIN FR_DIV_2STEP FR_BOX_FMA OR_BOX_FMA "
            "FR_SUM_PRIO FR_SUM_STUB FR_SUM_BUFLOAD FR_SUM_WAITFIX FR_SUM_DIRECT FR_SUM_THREADS FR_SUM_VGPRS "
-           "FR_SETUP_ON_TRACE_STREAM FR_QUEUE_MEMSET FR_TAIL_PRIO FR_KLENS FR_KSCAT kSkyDefer SKYD sky_dy RSTG SMAJ "
+           "FR_SETUP_ON_TRACE_STREAM FR_QUEUE_MEMSET FR_TAIL_PRIO FR_KLENS FR_KSCAT FR_OCCL_NEAR_FIRST kSkyDefer SKYD sky_dy RSTG SMAJ "
            "slot_at stage_base kStageSpansSub fine_item sum_kind jit_defines").split()
 TEXT = (".h", ".hip", ".cpp", ".py", ".sh", ".md", ".txt", ".json", ".inc")
 
