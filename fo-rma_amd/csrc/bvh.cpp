@@ -5,10 +5,13 @@
 #include "bvh.h"
 
 #include <math.h>
+#include <string.h>
 #include <stdlib.h>
 
 #include <algorithm>
 #include <vector>
+
+#include "refit.h"
 
 namespace fr {
 namespace {
@@ -35,8 +38,7 @@ struct Box3 {
 };
 
 // World bounds of one primitive; false for primitives that never hit (stubs) or
-// carry non-finite geometry (those stay out of the tree and can never be the winner
-// of the list loop either: their tests compare NaN). `reach` < 0: a sphere's own ball (the
+// carry non-finite geometry (build_range builds no tree over those). `reach` < 0: a sphere's own ball (the
 // scene's extent is taken from those); otherwise the ball its test accepts roots in for origins
 // within `reach` (bvh.h bvh_sphere_bound), which the tree is built over.
 bool prim_bounds(const fr_prim& p, Box3& b, float reach = -1.0f) {
@@ -289,7 +291,14 @@ bool build_range(const std::vector<fr_prim>& prims, uint32_t begin, uint32_t end
   items.reserve(end - begin);
   for (uint32_t i = begin; i < end; ++i) {
     Item it;
-    if (!prim_bounds(prims[i], it.box, reach)) continue;
+    if (!prim_bounds(prims[i], it.box, reach)) {
+      // Non-finite geometry has no bounds, and not every test refuses it: a box's slabs go through
+      // NaN-ignoring min / max, so a box with a NaN or infinite corner is hit by the list loop.
+      // Such a scene keeps the list loop; only stubs are left out of a tree.
+      const uint32_t k = prims[i].kind;
+      if (k == FR_SPHERE || k == FR_AABB || k == FR_OBB || k == FR_TRIANGLE) return false;
+      continue;
+    }
     for (int k = 0; k < 3; ++k) it.c[k] = 0.5f * (it.box.lo[k] + it.box.hi[k]);
     it.index = i;
     items.push_back(it);
@@ -364,6 +373,43 @@ bool build_segments(const std::vector<fr_prim>& prims, std::vector<BvhSegment>& 
     i = j;
   }
   return true;
+}
+
+bool bvh_prim_bounds(const fr_prim& p, float reach, RefitBox* out) {
+  Box3 b;
+  if (!prim_bounds(p, b, reach)) return false;
+  *out = RefitBox{{b.lo[0], b.lo[1], b.lo[2]}, 0.0f, {b.hi[0], b.hi[1], b.hi[2]}, 0.0f};
+  return true;
+}
+
+// The builder numbers a node before its children, so one backward sweep gives the heights.
+RefitSchedule bvh_refit_schedule(const std::vector<BvhNode>& nodes) {
+  RefitSchedule s;
+  const uint32_t n = static_cast<uint32_t>(nodes.size());
+  std::vector<uint8_t> h(n, 0);
+  uint32_t count[kBvhStack] = {};
+  for (uint32_t i = n; i-- > 0;) {
+    uint32_t hi = 0;
+    for (uint32_t r : nodes[i].ref)
+      if (r < kBvhLeaf) hi = std::max(hi, h[r] + 1u);
+    h[i] = static_cast<uint8_t>(std::min(hi, kBvhStack - 1u));
+    ++count[h[i]];
+  }
+  for (uint32_t k = 0; k < kBvhStack; ++k) {
+    s.offset[k + 1] = s.offset[k] + count[k];
+    if (count[k]) s.heights = k + 1;
+  }
+  s.ids.resize(n);
+  uint32_t at[kBvhStack];
+  memcpy(at, s.offset, sizeof(at));
+  for (uint32_t i = 0; i < n; ++i) s.ids[at[h[i]]++] = i;
+  return s;
+}
+
+void bvh_refit(std::vector<BvhNode>& nodes, const RefitSchedule& sched, const std::vector<RefitBox>& slot_bounds,
+               float pad, std::vector<RefitBox>& unions) {
+  unions.resize(nodes.size());
+  for (uint32_t id : sched.ids) refit_node(nodes[id], unions[id], slot_bounds.data(), unions.data(), pad);
 }
 
 float bvh_sphere_rmin(const std::vector<fr_prim>& prims) {

@@ -18,10 +18,14 @@ struct DeviceCopy;  // defined in render.hip (the upload of pack.h's blob)
 }  // namespace fr
 
 // The tracer's Scene (cpu_ray_tracer/scene.rs:4-7): an ordered primitive list.
-// Device copies are created lazily per device and dropped when `version` moves.
+// Device copies are created lazily per device and dropped when `version` moves. A geometric
+// edit (fr_scene_update) leaves `version` and advances `edit_seq`, with which
+// it stamps the primitives it replaced: a copy at an older sequence patches those in place.
 struct fr_scene {
   std::vector<fr_prim> prims;
   uint64_t version = 1;
+  uint64_t edit_seq = 0;
+  std::vector<uint64_t> stamp;  // per primitive, the sequence of its last geometric edit (empty: none yet)
   std::mutex mu;
   std::vector<fr::DeviceCopy*> copies;  // owned; freed by fr_scene_free
 };

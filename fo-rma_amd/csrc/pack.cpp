@@ -10,6 +10,7 @@
 #include <cmath>
 
 #include "bvh.h"
+#include "refit.h"
 #include "rt_core.h"
 
 namespace fr {
@@ -32,6 +33,51 @@ static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 struct F4 {
   float x, y, z, w;
 };
+
+void pack_record(const fr_prim& p, float rec[16]) {
+  uint32_t kind = p.kind;
+  F4 g[4] = {};
+  switch (p.kind) {
+    case FR_SPHERE: g[0] = F4{p.g[0], p.g[1], p.g[2], p.g[3]}; break;
+    case FR_AABB:
+      g[0] = F4{p.g[0], p.g[1], p.g[2], 0.0f};
+      g[1] = F4{p.g[3], p.g[4], p.g[5], 0.0f};
+      break;
+    case FR_PLANE:
+      g[0] = F4{p.g[0], p.g[1], p.g[2], 0.0f};
+      g[1] = F4{p.g[3], p.g[4], p.g[5], 0.0f};
+      g[2] = F4{p.g[6], p.g[7], p.g[8], 0.0f};
+      break;
+    case FR_OBB:
+      g[0] = F4{p.g[0], p.g[1], p.g[2], p.g[12]};
+      g[1] = F4{p.g[3], p.g[4], p.g[5], p.g[13]};
+      g[2] = F4{p.g[6], p.g[7], p.g[8], p.g[14]};
+      g[3] = F4{p.g[9], p.g[10], p.g[11], 0.0f};
+      break;
+    case FR_TRIANGLE: {
+      // v0, edges e1 = v1 - v0 and e2 = v2 - v0, and the unit winding normal
+      // unit(cross(e1, e2)), all in host f32 exactly as the oracle forms them
+      const V3 v0{p.g[0], p.g[1], p.g[2]};
+      const V3 e1 = sub(V3{p.g[3], p.g[4], p.g[5]}, v0), e2 = sub(V3{p.g[6], p.g[7], p.g[8]}, v0);
+      const V3 nw = unit(cross(e1, e2));
+      g[0] = F4{v0.x, v0.y, v0.z, 0.0f};
+      g[1] = F4{e1.x, e1.y, e1.z, 0.0f};
+      g[2] = F4{e2.x, e2.y, e2.z, 0.0f};
+      g[3] = F4{nw.x, nw.y, nw.z, 0.0f};
+      break;
+    }
+    default: kind = FR_STUB;
+  }
+  memcpy(&g[3].w, &kind, 4);  // kind bits in g3.w
+  memcpy(rec, g, 64);
+}
+
+void leaf_record(const float rec[16], float lrec[16]) {
+  memcpy(lrec, rec, 64);
+  uint32_t kind;
+  memcpy(&kind, &lrec[15], 4);
+  if (kind == FR_SPHERE) lrec[3] = lrec[3] * lrec[3];
+}
 
 PackedScene pack_scene(const std::vector<fr_prim>& prims, bool force_bvh) {
   PackedScene c;
@@ -74,6 +120,11 @@ PackedScene pack_scene(const std::vector<fr_prim>& prims, bool force_bvh) {
   table(c.off_runs, (runs.size() ? runs.size() : 4) * 4);
   table(c.off_acls, m * 4);
   table(c.off_acls_att, (kNibbleMaxPrims + 1) * 16);
+  // the refit's tables (refit.h), after everything the trace and walk kernels read
+  table(c.off_slot_bounds, (bvh_order.size() ? bvh_order.size() : 1) * sizeof(RefitBox));
+  table(c.off_slot_of, m * 4);
+  table(c.off_unions, (bvh_nodes.size() ? bvh_nodes.size() : 1) * sizeof(RefitBox));
+  table(c.off_sched, (bvh_nodes.size() ? bvh_nodes.size() : 1) * 4);
   std::vector<unsigned char>& host = c.bytes;
   host.assign(off, 0);
   std::vector<F4> aclass;  // distinct attenuations, first appearance order
@@ -91,39 +142,6 @@ PackedScene pack_scene(const std::vector<fr_prim>& prims, bool force_bvh) {
   sf.bvh_levels = bvh_ok ? std::min(bvh_max_depth(bvh_segs, bvh_nodes) + 1u, kBvhStack) : kBvhStack;
   for (uint32_t i = 0; i < n; ++i) {
     const fr_prim& p = prims[i];
-    uint32_t kind = p.kind;
-    F4 g[4] = {};
-    switch (p.kind) {
-      case FR_SPHERE: g[0] = F4{p.g[0], p.g[1], p.g[2], p.g[3]}; break;
-      case FR_AABB:
-        g[0] = F4{p.g[0], p.g[1], p.g[2], 0.0f};
-        g[1] = F4{p.g[3], p.g[4], p.g[5], 0.0f};
-        break;
-      case FR_PLANE:
-        g[0] = F4{p.g[0], p.g[1], p.g[2], 0.0f};
-        g[1] = F4{p.g[3], p.g[4], p.g[5], 0.0f};
-        g[2] = F4{p.g[6], p.g[7], p.g[8], 0.0f};
-        break;
-      case FR_OBB:
-        g[0] = F4{p.g[0], p.g[1], p.g[2], p.g[12]};
-        g[1] = F4{p.g[3], p.g[4], p.g[5], p.g[13]};
-        g[2] = F4{p.g[6], p.g[7], p.g[8], p.g[14]};
-        g[3] = F4{p.g[9], p.g[10], p.g[11], 0.0f};
-        break;
-      case FR_TRIANGLE: {
-        // v0, edges e1 = v1 - v0 and e2 = v2 - v0, and the unit winding normal
-        // unit(cross(e1, e2)), all in host f32 exactly as the oracle forms them
-        const V3 v0{p.g[0], p.g[1], p.g[2]};
-        const V3 e1 = sub(V3{p.g[3], p.g[4], p.g[5]}, v0), e2 = sub(V3{p.g[6], p.g[7], p.g[8]}, v0);
-        const V3 nw = unit(cross(e1, e2));
-        g[0] = F4{v0.x, v0.y, v0.z, 0.0f};
-        g[1] = F4{e1.x, e1.y, e1.z, 0.0f};
-        g[2] = F4{e2.x, e2.y, e2.z, 0.0f};
-        g[3] = F4{nw.x, nw.y, nw.z, 0.0f};
-        break;
-      }
-      default: kind = FR_STUB;
-    }
     const uint32_t cls = scatter_class(p);
     if (cls == SC_METAL || cls == SC_DIELECTRIC) sf.diffuse = false;
     const F4 mat{p.color[0], p.color[1], p.color[2], p.fuzz};
@@ -145,8 +163,9 @@ PackedScene pack_scene(const std::vector<fr_prim>& prims, bool force_bvh) {
     }
     for (float a : {att.x, att.y, att.z})
       if (!(a >= 0.0f) || std::signbit(a) || !std::isfinite(a)) c.att_nonneg = false;
-    memcpy(&g[3].w, &kind, 4);  // kind bits in g3.w
-    memcpy(&host[c.off_rec + 64 * i], g, 64);
+    float rec[16];
+    pack_record(p, rec);
+    memcpy(&host[c.off_rec + 64 * i], rec, 64);
     sf.has_plane |= p.kind == FR_PLANE;
     sf.kinds |= 1u << (p.kind <= FR_TRIANGLE ? p.kind : FR_STUB);
   }
@@ -161,13 +180,33 @@ PackedScene pack_scene(const std::vector<fr_prim>& prims, bool force_bvh) {
   // the BVH leaves' records, in leaf-slot order; a sphere's carries RN(radius^2) in place of
   // its radius, the product its hit test forms (sphere.rs:34; one VALU per leaf test saved)
   for (size_t slot = 0; slot < bvh_order.size(); ++slot) {
-    float lr[16];
-    memcpy(lr, &host[c.off_rec + 64 * static_cast<size_t>(bvh_order[slot])], 64);
-    uint32_t kind;
-    memcpy(&kind, &lr[15], 4);
-    if (kind == FR_SPHERE) lr[3] = lr[3] * lr[3];
+    float rec[16], lr[16];
+    memcpy(rec, &host[c.off_rec + 64 * static_cast<size_t>(bvh_order[slot])], 64);
+    leaf_record(rec, lr);
     memcpy(&host[c.off_lrec + 64 * slot], lr, 64);
   }
+  // the refit's tables: each slot's bounds as the builder took them, the slot of each primitive,
+  // the nodes' unpadded unions (bvh_refit over a copy of the nodes, which it reproduces) and the
+  // height schedule
+  c.slot_of.assign(m, kNoSlot);
+  c.n_slots = static_cast<uint32_t>(bvh_order.size());
+  c.n_nodes = static_cast<uint32_t>(bvh_nodes.size());
+  if (bvh_ok) {
+    const float reach = bvh_origin_reach(bvh_extent, sf.bvh_sphere_rmin);
+    std::vector<RefitBox> sb(bvh_order.size());
+    for (size_t slot = 0; slot < bvh_order.size(); ++slot) {
+      c.slot_of[bvh_order[slot]] = static_cast<uint32_t>(slot);
+      (void)bvh_prim_bounds(prims[bvh_order[slot]], reach, &sb[slot]);
+    }
+    c.sched = bvh_refit_schedule(bvh_nodes);
+    std::vector<RefitBox> unions;
+    std::vector<BvhNode> copy = bvh_nodes;  // (the blob holds the builder's own nodes)
+    bvh_refit(copy, c.sched, sb, 1e-4f * bvh_extent + 1e-4f, unions);
+    if (!sb.empty()) memcpy(&host[c.off_slot_bounds], sb.data(), sb.size() * sizeof(RefitBox));
+    if (!unions.empty()) memcpy(&host[c.off_unions], unions.data(), unions.size() * sizeof(RefitBox));
+    if (!c.sched.ids.empty()) memcpy(&host[c.off_sched], c.sched.ids.data(), c.sched.ids.size() * 4);
+  }
+  memcpy(&host[c.off_slot_of], c.slot_of.data(), m * 4);
   // entry n: the unit attenuation the depth-8 stack's empty levels point at
   memcpy(&host[c.off_att + 16 * n], &one, 16);
   if (n == 0) {

@@ -35,6 +35,7 @@
 #include "jit.h"
 #include "pack.h"
 #include "plan.h"
+#include "refit.h"
 #include "sum.h"
 #include "temporal.h"
 #include "trace_kernel.h"
@@ -48,13 +49,33 @@ static_assert(sizeof(fr_params) == 40, "fr_params layout");
 static_assert(sizeof(fr_stats) == 72, "fr_stats layout");
 static_assert(sizeof(fr_accum_error) == 32, "fr_accum_error layout");
 static_assert(sizeof(fr_adapt_info) == 56, "fr_adapt_info layout");
+static_assert(sizeof(fr_scene_info) == 72, "fr_scene_info layout");
 
 struct DeviceCopy {
   int device = -1;
   uint64_t version = 0;
-  uint64_t uid = 0;  // process-unique per upload: names these exact records (fr_ctx's kernel cache)
+  uint64_t edit_seq = 0;  // the scene's edit sequence these tables hold
+  uint64_t uid = 0;  // process-unique per upload or patch: names these exact records (fr_ctx's kernel cache)
   void* blob = nullptr;
   PackedScene ps;  // the blob's layout and facts (its bytes released after the upload)
+  // In-place catch-up: the staged rows (pinned host and device, reused: every patch starts with a
+  // device-wide wait, so the last copy out of them is done), the events around its parts and the
+  // event every user's streams wait for while it may be pending.
+  PatchRow* h_rows = nullptr;
+  PatchRow* d_rows = nullptr;
+  uint32_t cap_rows = 0;
+  hipEvent_t ev_part[3] = {};  // before the copy, after it, after the patch kernel
+  hipEvent_t ev_done = nullptr;
+  bool patch_pending = false;
+  float host_ms = 0.0f;  // the last patch's host preparation
+  uint64_t packs = 0, refits = 0;
+};
+
+// What one use of a scene did to its device copy (fr_ctx_scene_info).
+struct SceneSync {
+  const DeviceCopy* copy = nullptr;
+  uint32_t kind = FR_SCENE_SYNC_NONE, prims = 0, nodes = 0, launches = 0;
+  uint64_t refit_no = 0;  // the copy's refit count after it (its events are those of this patch)
 };
 
 // Sums the trace kernel's per-wave counters (KWork::wave_counters) into counters[0..2].
@@ -76,16 +97,119 @@ __global__ __launch_bounds__(256) void reduce_counters(const unsigned long long*
 
 // ---- device scene copies ----------------------------------------------------
 
-// The scene's copy on `device`: the cached one while the scene's version stands, else
-// packed (pack.h) and uploaded.
-static int upload_scene(fr_scene* s, int device, bool force_bvh, DeviceCopy** out) {
+static std::atomic<uint64_t> g_uploads{0};
+
+static RefitTables refit_tables(const DeviceCopy* c) {
+  char* b = static_cast<char*>(c->blob);
+  const PackedScene& ps = c->ps;
+  return RefitTables{reinterpret_cast<float4*>(b + ps.off_rec),
+                     reinterpret_cast<float4*>(b + ps.off_lrec),
+                     reinterpret_cast<BvhNode*>(b + ps.off_bvh),
+                     reinterpret_cast<RefitBox*>(b + ps.off_slot_bounds),
+                     reinterpret_cast<RefitBox*>(b + ps.off_unions),
+                     reinterpret_cast<const uint32_t*>(b + ps.off_slot_of),
+                     reinterpret_cast<const uint32_t*>(b + ps.off_sched),
+                     ps.facts.n,
+                     ps.n_slots,
+                     ps.n_nodes};
+}
+
+// A copy at the scene's version and an older edit sequence catches up in place (DESIGN.md
+// §4.7a): the primitives stamped since are packed on the host, copied and scattered, and every
+// node is refitted, on `stream`. *patched = false, with nothing enqueued or changed, when the
+// copy's tree cannot take an edit: a primitive whose own bounds leave the packed extent (the
+// packed padding and reach would fall below a fresh build's) or whose bounds verdict at the
+// packed reach is not its slot's. The caller re-packs then.
+static int patch_copy(fr_scene* s, DeviceCopy* c, hipStream_t stream, SceneSync* sync, bool* patched) {
+  *patched = false;
+  const auto t0 = std::chrono::steady_clock::now();
+  PackedScene& ps = c->ps;
+  const uint32_t n = static_cast<uint32_t>(s->prims.size());
+  if (ps.facts.n != n || s->stamp.size() != n) return FR_OK;
+  const bool tree = ps.facts.bvh_ok && ps.n_nodes + ps.n_slots > 0;
+  const float extent = ps.facts.bvh_extent;
+  const float reach = bvh_origin_reach(extent, ps.facts.bvh_sphere_rmin);
+  std::vector<uint32_t> ids;
+  for (uint32_t i = 0; i < n; ++i)
+    if (s->stamp[i] > c->edit_seq) ids.push_back(i);
+  const uint32_t m = static_cast<uint32_t>(ids.size());
+  if (tree)
+    for (uint32_t i : ids) {
+      RefitBox own, at_reach;
+      if (bvh_prim_bounds(s->prims[i], -1.0f, &own))
+        for (int k = 0; k < 3; ++k)
+          if (!(fabsf(own.lo[k]) <= extent) || !(fabsf(own.hi[k]) <= extent)) return FR_OK;
+      if (bvh_prim_bounds(s->prims[i], reach, &at_reach) != (ps.slot_of[i] != kNoSlot)) return FR_OK;
+    }
+  // write-after-read: everything enqueued on this device so far reads the old tables
+  HIPCHK(hipDeviceSynchronize());
+  if (m > c->cap_rows) {
+    if (c->h_rows) HIPCHK(hipHostFree(c->h_rows));
+    if (c->d_rows) HIPCHK(hipFree(c->d_rows));
+    c->h_rows = c->d_rows = nullptr;
+    c->cap_rows = 0;
+    HIPCHK(hipHostMalloc(&c->h_rows, static_cast<size_t>(m) * sizeof(PatchRow), hipHostMallocDefault));
+    HIPCHK(hipMalloc(&c->d_rows, static_cast<size_t>(m) * sizeof(PatchRow)));
+    c->cap_rows = m;
+  }
+  if (!c->ev_done) {
+    for (hipEvent_t& e : c->ev_part) HIPCHK(hipEventCreate(&e));
+    HIPCHK(hipEventCreate(&c->ev_done));
+  }
+  for (uint32_t k = 0; k < m; ++k) {
+    const fr_prim& p = s->prims[ids[k]];
+    PatchRow& r = c->h_rows[k];
+    r = PatchRow{};
+    r.index = ids[k];
+    pack_record(p, r.rec);
+    leaf_record(r.rec, r.lrec);
+    r.bounds = refit_empty();
+    if (tree) (void)bvh_prim_bounds(p, reach, &r.bounds);
+    memcpy(&ps.rec_words[16u * static_cast<size_t>(ids[k])], r.rec, 64);  // the scene-specialised build's constants
+  }
+  c->host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  const RefitTables t = refit_tables(c);
+  uint32_t launches = 0;
+  HIPCHK(hipEventRecord(c->ev_part[0], stream));
+  if (m) HIPCHK(hipMemcpyAsync(c->d_rows, c->h_rows, static_cast<size_t>(m) * sizeof(PatchRow), hipMemcpyHostToDevice, stream));
+  HIPCHK(hipEventRecord(c->ev_part[1], stream));
+  if (m) HIPCHK(launch_scene_patch(stream, t, c->d_rows, m));
+  HIPCHK(hipEventRecord(c->ev_part[2], stream));
+  if (tree && m) HIPCHK(launch_bvh_refit(stream, t, ps.sched, 1e-4f * extent + 1e-4f, &launches));
+  HIPCHK(hipEventRecord(c->ev_done, stream));
+  c->patch_pending = true;
+  c->edit_seq = s->edit_seq;
+  c->uid = ++g_uploads;
+  ++c->refits;
+  *sync = SceneSync{c, FR_SCENE_SYNC_REFIT, m, launches ? ps.n_nodes : 0u, launches, c->refits};
+  *patched = true;
+  return FR_OK;
+}
+
+// The scene's copy on `device`: the cached one while the scene's version and edit sequence
+// stand, patched in place when only the sequence moved (patch_copy, on streams[0]), else packed
+// (pack.h) and uploaded. While a patch may be pending, every stream of `streams` (the ones the
+// caller reads the scene on) waits for it.
+static int upload_scene(fr_scene* s, int device, bool force_bvh, DeviceCopy** out, const hipStream_t (&streams)[3],
+                        SceneSync* sync) {
   std::lock_guard<std::mutex> g(s->mu);
   DeviceCopy* c = nullptr;
   for (DeviceCopy* e : s->copies)
     if (e->device == device) c = e;
+  *sync = SceneSync{c};
   if (c && c->version == s->version) {
-    *out = c;
-    return FR_OK;
+    bool current = c->edit_seq == s->edit_seq;
+    if (!current) {
+      const int rc = patch_copy(s, c, streams[0], sync, &current);
+      if (rc) return rc;
+    }
+    if (current) {
+      if (c->patch_pending && hipEventQuery(c->ev_done) == hipSuccess) c->patch_pending = false;
+      if (c->patch_pending)
+        for (hipStream_t st : streams) HIPCHK(hipStreamWaitEvent(st, c->ev_done, 0));
+      *out = c;
+      return FR_OK;
+    }
   }
   if (!c) {
     c = new DeviceCopy();
@@ -99,8 +223,11 @@ static int upload_scene(fr_scene* s, int device, bool force_bvh, DeviceCopy** ou
   HIPCHK(hipMemcpy(c->blob, c->ps.bytes.data(), c->ps.bytes.size(), hipMemcpyHostToDevice));
   std::vector<unsigned char>().swap(c->ps.bytes);
   c->version = s->version;
-  static std::atomic<uint64_t> g_uploads{0};
+  c->edit_seq = s->edit_seq;
+  c->patch_pending = false;
   c->uid = ++g_uploads;
+  ++c->packs;
+  *sync = SceneSync{c, FR_SCENE_SYNC_PACK, 0, 0, 0, c->refits};
   *out = c;
   return FR_OK;
 }
@@ -113,6 +240,11 @@ void release_device_copies(fr_scene* s) {
       if (hipGetDevice(&cur) == hipSuccess) {
         (void)hipSetDevice(c->device);
         (void)hipFree(c->blob);
+        if (c->d_rows) (void)hipFree(c->d_rows);
+        if (c->h_rows) (void)hipHostFree(c->h_rows);
+        for (hipEvent_t e : c->ev_part)
+          if (e) (void)hipEventDestroy(e);
+        if (c->ev_done) (void)hipEventDestroy(c->ev_done);
         (void)hipSetDevice(cur);
       }
     }
@@ -301,7 +433,16 @@ struct fr_ctx {
   // log 3: every cast kernel and G-buffer pass, on the sum stream
   std::vector<hipEvent_t> log_ev[4];  // 2 per entry (start, end); reused across logs
   size_t log_n[4] = {0, 0, 0, 0};     // entries logged
+  // what this context's last use of a scene did to the scene's device copy (fr_ctx_scene_info)
+  SceneSync scene_sync{};
 };
+
+// The scene's device copy for a call of this context, caught up (upload_scene): a patch goes on
+// the context's first trace stream, and the streams its kernels read scenes on wait for it.
+static int ctx_scene(fr_ctx* c, fr_scene* scene, bool force_bvh, DeviceCopy** out) {
+  const hipStream_t streams[3] = {c->stream, c->stream2, c->stream_sum};
+  return upload_scene(scene, c->device, force_bvh, out, streams, &c->scene_sync);
+}
 
 static hipError_t log_event(fr_ctx* c, int which, size_t k, hipStream_t st) {
   std::vector<hipEvent_t>& v = c->log_ev[which];
@@ -792,7 +933,7 @@ static int render_impl(fr_ctx* c, fr_scene* scene, const fr_camera* cam, const f
   SET_DEVICE(c->device);
   const PlanEnv env = read_plan_env();
   DeviceCopy* dc = nullptr;
-  if ((rc = upload_scene(scene, c->device, env.bvh_force, &dc))) return rc;
+  if ((rc = ctx_scene(c, scene, env.bvh_force, &dc))) return rc;
   const size_t pixels = static_cast<size_t>(p->width) * p->height;
   if (pixels * 3 * sizeof(float) > c->cap_mean && c->copy_pending)
     HIPCHK(hipStreamSynchronize(c->stream_copy));  // a gather still reads them
@@ -1323,6 +1464,70 @@ static CastScene cast_scene(const DeviceCopy* dc) {
   return cs;
 }
 
+// What this context's last use of `scene` did to the scene's copy on its device, and the copy's
+// running counts. The device times of a refit read -1 while it is pending.
+int fr_ctx_scene_info(fr_ctx* c, fr_scene* scene, fr_scene_info* out) {
+  if (!c || !scene || !out) return set_error(FR_EARG, "fr_ctx_scene_info: null argument");
+  SET_DEVICE(c->device);
+  std::lock_guard<std::mutex> g(scene->mu);
+  const DeviceCopy* dc = nullptr;
+  for (const DeviceCopy* e : scene->copies)
+    if (e->device == c->device) dc = e;
+  *out = fr_scene_info{};
+  out->h2d_ms = out->patch_ms = out->refit_ms = -1.0f;
+  out->version = scene->version;
+  out->edit_seq = scene->edit_seq;
+  if (!dc) return FR_OK;
+  out->packs = dc->packs;
+  out->refits = dc->refits;
+  out->has_tree = dc->ps.facts.bvh_ok ? 1u : 0u;
+  out->n_nodes = dc->ps.n_nodes;
+  const SceneSync& sy = c->scene_sync;
+  if (sy.copy != dc) return FR_OK;
+  out->last_sync = sy.kind;
+  out->prims_patched = sy.prims;
+  out->nodes_refit = sy.nodes;
+  out->refit_launches = sy.launches;
+  if (sy.kind == FR_SCENE_SYNC_REFIT && sy.refit_no == dc->refits) {
+    out->host_ms = dc->host_ms;
+    if (hipEventQuery(dc->ev_done) == hipSuccess) {
+      HIPCHK(hipEventElapsedTime(&out->h2d_ms, dc->ev_part[0], dc->ev_part[1]));
+      HIPCHK(hipEventElapsedTime(&out->patch_ms, dc->ev_part[1], dc->ev_part[2]));
+      HIPCHK(hipEventElapsedTime(&out->refit_ms, dc->ev_part[2], dc->ev_done));
+    }
+  }
+  return FR_OK;
+}
+
+// One table of the scene's copy on `device` as it stands (a copy that is behind the list is not
+// caught up), after a device-wide wait. out NULL: *bytes only.
+int fr_scene_download_table(fr_scene* scene, int device, uint32_t which, void* out, size_t cap, size_t* bytes) {
+  if (!scene || (!out && !bytes)) return set_error(FR_EARG, "fr_scene_download_table: null argument");
+  std::lock_guard<std::mutex> g(scene->mu);
+  const DeviceCopy* dc = nullptr;
+  for (const DeviceCopy* e : scene->copies)
+    if (e->device == device) dc = e;
+  if (!dc || !dc->blob) return set_error(FR_EARG, "fr_scene_download_table: the scene has no copy on device %d", device);
+  const PackedScene& ps = dc->ps;
+  size_t off = 0, size = 0;
+  switch (which) {
+    case FR_TABLE_RECORDS: off = ps.off_rec, size = 64u * static_cast<size_t>(ps.facts.n); break;
+    case FR_TABLE_LEAF_RECORDS: off = ps.off_lrec, size = 64u * static_cast<size_t>(ps.n_slots); break;
+    case FR_TABLE_LEAF_ORDER: off = ps.off_bvh_order, size = 4u * static_cast<size_t>(ps.n_slots); break;
+    case FR_TABLE_NODES: off = ps.off_bvh, size = sizeof(BvhNode) * static_cast<size_t>(ps.n_nodes); break;
+    case FR_TABLE_SLOT_BOUNDS: off = ps.off_slot_bounds, size = sizeof(RefitBox) * static_cast<size_t>(ps.n_slots); break;
+    case FR_TABLE_NODE_UNIONS: off = ps.off_unions, size = sizeof(RefitBox) * static_cast<size_t>(ps.n_nodes); break;
+    default: return set_error(FR_EARG, "fr_scene_download_table: unknown table %u", which);
+  }
+  if (bytes) *bytes = size;
+  if (!out) return FR_OK;
+  if (cap < size) return set_error(FR_EARG, "fr_scene_download_table: %zu bytes, the buffer holds %zu", size, cap);
+  SET_DEVICE(device);
+  HIPCHK(hipDeviceSynchronize());
+  if (size) HIPCHK(hipMemcpy(out, static_cast<const char*>(dc->blob) + off, size, hipMemcpyDeviceToHost));
+  return FR_OK;
+}
+
 // The view's feature buffers: one pass on the sum stream, behind whatever is
 // enqueued there; nothing is waited for. Frames, A, Q, d_mean, d_u8, the pending render and its
 // stats are untouched: the pass reads the scene's device copy and writes buffers of its own.
@@ -1335,7 +1540,7 @@ int fr_ctx_gbuffer(fr_ctx* c, fr_scene* scene, const fr_camera* cam, uint32_t wi
   const PlanEnv env = read_plan_env();
   DeviceCopy* dc = nullptr;
   int rc;
-  if ((rc = upload_scene(scene, c->device, env.bvh_force, &dc))) return rc;
+  if ((rc = ctx_scene(c, scene, env.bvh_force, &dc))) return rc;
   if (c->gb_w != width || c->gb_h != height || !c->d_gb_alb) {
     HIPCHK(hipStreamSynchronize(c->stream_sum));  // the kernels and copies that use the old buffers
     c->gb_valid = false;
@@ -1463,7 +1668,7 @@ int fr_ctx_cast(fr_ctx* c, fr_scene* scene, const fr_ray* rays, uint32_t n, uint
   const PlanEnv env = read_plan_env();
   DeviceCopy* dc = nullptr;
   int rc;
-  if ((rc = upload_scene(scene, c->device, env.bvh_force, &dc))) return rc;
+  if ((rc = ctx_scene(c, scene, env.bvh_force, &dc))) return rc;
   if (n > c->cast_cap || !c->d_cast_waves) {
     HIPCHK(hipStreamSynchronize(c->stream_sum));  // the kernels and copies that use the old buffers
     c->cast_valid = false;
@@ -1548,7 +1753,7 @@ int fr_ctx_occluded(fr_ctx* c, fr_scene* scene, const fr_ray* rays, uint32_t n, 
   const PlanEnv env = read_plan_env();
   DeviceCopy* dc = nullptr;
   int rc;
-  if ((rc = upload_scene(scene, c->device, env.bvh_force, &dc))) return rc;
+  if ((rc = ctx_scene(c, scene, env.bvh_force, &dc))) return rc;
   if (!c->d_occl_waves) HIPCHK(hipMalloc(&c->d_occl_waves, kCastWaveBytes));
   if (!out_device && n > c->occl_cap) {
     HIPCHK(hipStreamSynchronize(c->stream_sum));  // the kernels and copies that use the old bytes

@@ -15,6 +15,7 @@
 #include "internal.h"
 #include "json_min.h"
 #include "gbuffer.h"
+#include "refit.h"
 #include "rt_core.h"
 
 namespace fr {
@@ -635,6 +636,52 @@ int fr_scene_rotate(fr_scene* s, uint32_t i, const float v[3]) {
     memcpy(s->prims[i].g + 3, v, 3 * sizeof(float));
     ++s->version;
   }
+  return FR_OK;
+}
+
+// Replaces primitives of the list. Geometric: every listed primitive keeps
+// its kind, material, colour and fuzz bit for bit and its prim_bounds verdict (bounds or none);
+// such an edit stamps the primitives with a new edit sequence, which the device copies catch up
+// with in place. Anything else is an edit of the version, the full re-pack.
+int fr_scene_update(fr_scene* s, const uint32_t* index, const fr_prim* prims, uint32_t n, uint32_t flags) {
+  if (!s || (n && !prims)) return set_error(FR_EARG, "fr_scene_update: bad arguments");
+  if (flags & ~static_cast<uint32_t>(FR_UPDATE_REBUILD)) return set_error(FR_EARG, "fr_scene_update: unknown flags 0x%x", flags);
+  std::lock_guard<std::mutex> g(s->mu);
+  const size_t count = s->prims.size();
+  if (!index && n > count) return set_error(FR_EARG, "fr_scene_update: n %u > count %zu without an index list", n, count);
+  for (uint32_t k = 0; k < n; ++k) {
+    if (index && index[k] >= count)
+      return set_error(FR_EARG, "fr_scene_update: index[%u] = %u, the scene has %zu primitives", k, index[k], count);
+    if (prims[k].kind > FR_TRIANGLE) return set_error(FR_EARG, "fr_scene_update: prims[%u] has unknown kind %u", k, prims[k].kind);
+  }
+  if (n == 0 && !(flags & FR_UPDATE_REBUILD)) return FR_OK;
+  bool geometric = !(flags & FR_UPDATE_REBUILD);
+  for (uint32_t k = 0; k < n && geometric; ++k) {
+    const fr_prim& was = s->prims[index ? index[k] : k];
+    const fr_prim& p = prims[k];
+    RefitBox b;
+    geometric = p.kind == was.kind && p.material == was.material && memcmp(p.color, was.color, sizeof(p.color)) == 0 &&
+                memcmp(&p.fuzz, &was.fuzz, sizeof(p.fuzz)) == 0 &&
+                bvh_prim_bounds(p, -1.0f, &b) == bvh_prim_bounds(was, -1.0f, &b);
+  }
+  if (geometric) {
+    if (s->stamp.size() != count) s->stamp.assign(count, 0);
+    ++s->edit_seq;
+  } else {
+    ++s->version;
+  }
+  for (uint32_t k = 0; k < n; ++k) {
+    const uint32_t i = index ? index[k] : k;
+    s->prims[i] = prims[k];
+    if (geometric) s->stamp[i] = s->edit_seq;
+  }
+  return FR_OK;
+}
+
+int fr_scene_rebuild(fr_scene* s) {
+  if (!s) return set_error(FR_EARG, "fr_scene_rebuild: null scene");
+  std::lock_guard<std::mutex> g(s->mu);
+  ++s->version;
   return FR_OK;
 }
 

@@ -138,6 +138,23 @@ class FrOcclInfo(C.Structure):
                 ("occluded", C.c_uint32), ("pad", C.c_uint32 * 3)]
 
 
+class FrSceneInfo(C.Structure):
+    _fields_ = [("last_sync", C.c_uint32), ("prims_patched", C.c_uint32), ("nodes_refit", C.c_uint32),
+                ("refit_launches", C.c_uint32), ("packs", C.c_uint64), ("refits", C.c_uint64),
+                ("version", C.c_uint64), ("edit_seq", C.c_uint64), ("host_ms", C.c_float), ("h2d_ms", C.c_float),
+                ("patch_ms", C.c_float), ("refit_ms", C.c_float), ("has_tree", C.c_uint32), ("n_nodes", C.c_uint32)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+# moving scenes (forma_rt.h): fr_scene_update's flag, what a use did to the device copy, the tables
+FR_UPDATE_REBUILD = 1
+FR_SCENE_SYNC_NONE, FR_SCENE_SYNC_PACK, FR_SCENE_SYNC_REFIT = 0, 1, 2
+FR_TABLE_RECORDS, FR_TABLE_LEAF_RECORDS, FR_TABLE_LEAF_ORDER, FR_TABLE_NODES = 0, 1, 2, 3
+FR_TABLE_SLOT_BOUNDS, FR_TABLE_NODE_UNIONS = 4, 5
+_TABLES = {"records": 0, "leaf_records": 1, "leaf_order": 2, "nodes": 3, "slot_bounds": 4, "node_unions": 5}
+
 # fr_ctx_cast / fr_ctx_occluded flags (forma_rt.h)
 FR_CAST_LIST = 1
 FR_CAST_RAYS_DEVICE = 2
@@ -168,6 +185,7 @@ EXPORTS = (
     "fr_ctx_temporal", "fr_ctx_temporal_reset", "fr_ctx_download_temporal",
     "fr_ctx_gbuffer_info", "fr_camera_pixel_ray", "fr_ctx_cast", "fr_ctx_download_hits", "fr_ctx_cast_info",
     "fr_ctx_hit_buffers", "fr_ctx_occluded", "fr_ctx_download_occluded", "fr_ctx_occluded_info",
+    "fr_scene_update", "fr_scene_rebuild", "fr_ctx_scene_info", "fr_scene_download_table",
 )
 
 _lib = None
@@ -302,6 +320,11 @@ def lib():
         L.fr_ctx_occluded.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32, vp]
         L.fr_ctx_download_occluded.argtypes = [vp, vp]
         L.fr_ctx_occluded_info.argtypes = [vp, P(FrOcclInfo)]
+    if hasattr(L, "fr_scene_update"):
+        L.fr_scene_update.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32]
+        L.fr_scene_rebuild.argtypes = [vp]
+        L.fr_ctx_scene_info.argtypes = [vp, vp, P(FrSceneInfo)]
+        L.fr_scene_download_table.argtypes = [vp, C.c_int, C.c_uint32, vp, C.c_size_t, P(C.c_size_t)]
     _lib = L
     return L
 
@@ -412,6 +435,17 @@ class Stub(Hitable):
 
 # ---- scenes and cameras -----------------------------------------------------
 
+def _prim_of(p):
+    """FrPrim of a dict with kind / material / color / fuzz / g."""
+    q = FrPrim()
+    q.kind, q.material, q.fuzz = p["kind"], p["material"], float(p["fuzz"])
+    for k in range(3):
+        q.color[k] = float(p["color"][k])
+    for k in range(16):
+        q.g[k] = float(p["g"][k])
+    return q
+
+
 class Scene:
     """An ordered primitive list on the host plus its resident device copies
     (cpu_ray_tracer/scene.rs:4-7)."""
@@ -479,6 +513,63 @@ class Scene:
 
     def rotate(self, index, v):
         check(lib().fr_scene_rotate(self._h, index, _f3(v)))
+
+    def update(self, indices, prims_or_objects, rebuild=False):
+        """Replace primitives (fr_scene_update): indices None means 0..n-1. prims_or_objects holds
+        FrPrim, Hitable objects or oracle-style dicts, or is an [n, 22] uint32 array of fr_prim
+        words. A geometric edit is caught up in place on the device; rebuild=True forces the
+        full re-pack."""
+        if isinstance(prims_or_objects, np.ndarray):
+            words = np.ascontiguousarray(prims_or_objects, np.uint32).reshape(-1, 22)
+            n, pptr = len(words), words.ctypes.data
+        else:
+            items = list(prims_or_objects)
+            n = len(items)
+            arr = (FrPrim * max(1, n))()
+            for i, p in enumerate(items):
+                arr[i] = p if isinstance(p, FrPrim) else p.to_prim() if isinstance(p, Hitable) else _prim_of(p)
+            pptr = C.addressof(arr)
+        idx = None
+        if indices is not None:
+            idx = np.ascontiguousarray(indices, np.uint32).reshape(-1)
+            if len(idx) != n:
+                raise ValueError(f"update: {len(idx)} indices for {n} primitives")
+        check(lib().fr_scene_update(self._h, idx.ctypes.data if idx is not None and n else None, pptr if n else None, n,
+                                    FR_UPDATE_REBUILD if rebuild else 0))
+
+    def set_spheres(self, indices, centers, radii=None):
+        """Move the spheres at `indices` (None: primitives 0..n-1) to `centers` [n, 3], with new
+        `radii` [n] if given: one fr_scene_update of the list's own primitives with the geometry
+        replaced, formed in numpy."""
+        centers = np.asarray(centers, np.float32).reshape(-1, 3)
+        n = len(centers)
+        count = len(self)
+        idx = np.arange(n, dtype=np.uint32) if indices is None else np.ascontiguousarray(indices, np.uint32).reshape(-1)
+        if len(idx) != n or (n and int(idx.max()) >= count):
+            raise ValueError("set_spheres: indices do not match the centers or the scene")
+        words = np.zeros((max(1, count), 22), np.uint32)
+        check(lib().fr_scene_get_prims(self._h, words.ctypes.data_as(C.POINTER(FrPrim)), count))
+        sel = words[idx]
+        if n and not (sel[:, 0] == FR_SPHERE).all():
+            raise ValueError("set_spheres: a listed primitive is not a sphere")
+        sel[:, 6:9] = centers.view(np.uint32)
+        if radii is not None:
+            sel[:, 9] = np.ascontiguousarray(np.broadcast_to(np.asarray(radii, np.float32), (n,))).view(np.uint32)
+        self.update(idx, sel)
+
+    def rebuild(self):
+        """The next use packs and builds the scene again (fr_scene_rebuild)."""
+        check(lib().fr_scene_rebuild(self._h))
+
+    def download_table(self, device, which):
+        """One table of the device copy as a uint32 array [rows, words per row] (diagnostics; waits):
+        "records", "leaf_records", "nodes" (16 words), "leaf_order" (1), "slot_bounds", "node_unions" (8)."""
+        w = _TABLES[which] if isinstance(which, str) else int(which)
+        size = C.c_size_t(0)
+        check(lib().fr_scene_download_table(self._h, device, w, None, 0, C.byref(size)))
+        out = np.zeros(size.value // 4, np.uint32)
+        check(lib().fr_scene_download_table(self._h, device, w, out.ctypes.data, out.nbytes, C.byref(size)))
+        return out.reshape(-1, {2: 1, 4: 8, 5: 8}.get(w, 16))
 
     def close(self):
         if self._h and self._h.value:
@@ -751,6 +842,13 @@ class RenderContext:
         check(lib().fr_ctx_download_gbuffer(self._h, out["prim"].ctypes.data_as(C.POINTER(C.c_uint32)), fp(out["depth"]),
                                             fp(out["normal"]), fp(out["position"]), fp(out["albedo"])))
         return out
+
+    def scene_info(self, scene):
+        """What this context's last use of `scene` did to its device copy (fr_ctx_scene_info): a dict
+        with last_sync (FR_SCENE_SYNC_*), prims_patched, nodes_refit, refit_launches, packs, refits."""
+        info = FrSceneInfo()
+        check(lib().fr_ctx_scene_info(self._h, scene._h, C.byref(info)))
+        return info.as_dict()
 
     def gbuffer_info(self):
         """"tree" or "list": the walk the last gbuffer() took (fr_ctx_gbuffer_info). No wait."""

@@ -70,6 +70,8 @@ extern "C" {
    fr_ctx_cast_info, fr_ctx_gbuffer_info; fr_ctx_trace_log_read which = 5) */
 /* (still 6, additive too: FR_CAST_TMAX, FR_CAST_OUT_DEVICE, fr_occl_info, fr_ctx_occluded,
    fr_ctx_download_occluded, fr_ctx_occluded_info, fr_ctx_hit_buffers) */
+/* (still 6, additive too: FR_UPDATE_REBUILD, FR_SCENE_SYNC_*, FR_TABLE_*, fr_scene_info, fr_scene_update,
+   fr_scene_rebuild, fr_ctx_scene_info, fr_scene_download_table) */
 
 /* error codes */
 #define FR_OK 0
@@ -273,6 +275,55 @@ uint32_t fr_scene_count(const fr_scene* scene);
 int fr_scene_get_prims(const fr_scene* scene, fr_prim* out, uint32_t n);
 int fr_scene_translate(fr_scene* scene, uint32_t index, const float v[3]);
 int fr_scene_rotate(fr_scene* scene, uint32_t index, const float v[3]);
+
+/* Moving scenes. fr_scene_update replaces the n listed primitives of the host
+   list (index NULL: primitives 0..n-1; duplicates allowed, the last one wins). Every index is
+   checked first: one out of range, or an unknown kind, is FR_EARG and nothing moves. n = 0 is a
+   no-op. The edit is geometric when every listed primitive keeps the kind, material, colour and
+   fuzz of the one it replaces, bit for bit, and stays boundable or not (finite box, sphere,
+   oriented box or triangle: boundable; plane, stub, non-finite geometry: not). A geometric edit
+   keeps the scene's device copies: each patches the edited primitives' records in place and refits
+   its tree's boxes on the device, inside the first render, cast, G-buffer or occlusion call after
+   the edit (when a moved primitive leaves the extent the tree was padded for, that copy is packed
+   and built again instead: fr_ctx_scene_info says which happened). Any other edit, and any call
+   with FR_UPDATE_REBUILD, takes the path of fr_scene_translate: pack, build, upload. Either way
+   the scene counts as edited: an accumulation restarts, a G-buffer of the old scene is refused.
+   fr_scene_rebuild asks for that full path at the next use (a refitted tree keeps its topology
+   and walks slower the further the primitives have moved).
+   Ordering: work enqueued before the catch-up, on any stream of any context of that device, reads
+   the old scene (the catch-up starts with a device-wide wait); work enqueued after it reads the
+   new one, on whichever context: a context that finds the copy already caught up has its streams
+   wait for the patch. Calls that use one scene from several threads must not overlap an update. */
+#define FR_UPDATE_REBUILD 1u
+#define FR_SCENE_SYNC_NONE 0u  /* the copy was current */
+#define FR_SCENE_SYNC_PACK 1u  /* packed, built and uploaded */
+#define FR_SCENE_SYNC_REFIT 2u /* patched in place, tree refitted */
+typedef struct fr_scene_info {
+  uint32_t last_sync;      /* FR_SCENE_SYNC_*: what this context's last call that used the scene did to the copy */
+  uint32_t prims_patched;  /* _REFIT: primitives rewritten */
+  uint32_t nodes_refit;    /* _REFIT: tree nodes recomputed (0: the copy has no tree) */
+  uint32_t refit_launches; /* _REFIT: refit kernel launches (one per tree height) */
+  uint64_t packs, refits;  /* the copy's running counts */
+  uint64_t version, edit_seq; /* the host list's */
+  float host_ms;           /* _REFIT: host preparation of the rows */
+  float h2d_ms, patch_ms, refit_ms; /* _REFIT: its copy, patch kernel and refit launches by device events; -1 while pending */
+  uint32_t has_tree, n_nodes;
+} fr_scene_info;
+int fr_scene_update(fr_scene* scene, const uint32_t* index /* NULL: 0..n-1 */, const fr_prim* prims, uint32_t n, uint32_t flags);
+int fr_scene_rebuild(fr_scene* scene);
+/* Diagnostics: one table of the scene's copy on `device`, as it stands, after a device-wide wait.
+   out NULL: *bytes receives the size only. FR_EARG when the scene has no copy there or cap is short. */
+#define FR_TABLE_RECORDS 0u      /* 64 B per primitive, list order */
+#define FR_TABLE_LEAF_RECORDS 1u /* 64 B per leaf slot */
+#define FR_TABLE_LEAF_ORDER 2u   /* uint32 per leaf slot: the list index */
+#define FR_TABLE_NODES 3u        /* 64 B per tree node */
+#define FR_TABLE_SLOT_BOUNDS 4u  /* 32 B per leaf slot: lo xyz, 0, hi xyz, 0 */
+#define FR_TABLE_NODE_UNIONS 5u  /* 32 B per tree node, unpadded */
+int fr_scene_download_table(fr_scene* scene, int device, uint32_t which, void* out, size_t cap, size_t* bytes);
+/* What this context's last call that used `scene` did to the scene's copy on the context's device
+   (a second context that finds the copy caught up reads FR_SCENE_SYNC_NONE), and that copy's counts.
+   Nothing is waited for. */
+int fr_ctx_scene_info(fr_ctx* ctx, fr_scene* scene, fr_scene_info* out);
 
 /* ---- camera (host; tan/cos/sin are host-only) ---- */
 int fr_camera_init(fr_camera* cam, uint32_t width, uint32_t height);

@@ -1,0 +1,310 @@
+// refit_check.cpp — test harness (tests/test_refit_host.py, tests/test_refit_fixtures.py): the
+// in-place scene edit's host definition (fo-rma_amd/csrc/refit.h, bvh.cpp bvh_refit, pack.cpp
+// pack_record / leaf_record) as a CPU program, built with -fsanitize=address,undefined
+// -fno-sanitize-recover=all -ffp-contract=off together with pack.cpp and bvh.cpp.
+//   refit_check FILE [TABLES]
+// FILE holds u32 words: n, m, k, force, then n fr_prim (22 words each), then k edits (an index and
+// the 22 words of the primitive that replaces it), then m rays (8 words: o, pad, d, pad).
+// It packs the n primitives (force: with the tree forced) and checks
+//   refit    nodes that bvh_refit over the unmoved slots' bounds does not reproduce byte for byte,
+//            plus differences between the blob's slot-bounds / union tables and the recomputed ones
+//   sched    faults of the height schedule (a node listed twice or never, or before a child)
+// then applies the k edits as the library does (records, leaf records and bounds of the edited
+// primitives, every node refitted) and checks over the m rays, with cast.h's host walks,
+//   mismatch rays that pass the fallback test whose tree walk differs from the list loop
+//   stale    the same count for the OLD nodes with the new records (the control: it must not be 0
+//            for a move that leaves the old boxes)
+//   restore  tables that differ from the first pack's after the edited primitives are put back
+// and reports `patchable` (1: every edit keeps its bounds verdict and its own bounds lie within
+// the packed extent, the library's condition for patching in place). One line
+//   info tree T nodes N slots S heights H patchable P refit R sched C mismatch M stale X restore B
+// then per edit `topo INDEX SLOT LEAF PARENT SIDE` (the first slot of its leaf, the node that
+// references the leaf, which child of its tree's root it lies under; ffffffff: none), then one line
+// per ray as cast_check prints it (the list loop over the edited records). TABLES, if given,
+// receives the edited tables: 4 words (n, slots, nodes, 0), the records, the leaf records, the leaf
+// order and the nodes. Exit status 1 if R, C, M or B is not 0.
+#include <math.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <string.h>
+
+#include <vector>
+
+#include "../../fo-rma_amd/csrc/cast.h"
+#include "../../fo-rma_amd/csrc/pack.h"
+#include "../../fo-rma_amd/csrc/refit.h"
+
+namespace {
+
+float as_f32(uint32_t b) {
+  float f;
+  memcpy(&f, &b, 4);
+  return f;
+}
+uint32_t bits(float f) {
+  uint32_t u;
+  memcpy(&u, &f, 4);
+  return u;
+}
+
+struct Tables {
+  std::vector<float> rec, lrec;
+  std::vector<uint32_t> order;
+  std::vector<fr::BvhNode> nodes;
+  std::vector<fr::RefitBox> slot_bounds, unions;
+};
+
+bool same_bytes(const Tables& a, const Tables& b) {
+  auto eq = [](const void* x, const void* y, size_t n) { return n == 0 || memcmp(x, y, n) == 0; };
+  return a.rec.size() == b.rec.size() && a.lrec.size() == b.lrec.size() && a.nodes.size() == b.nodes.size() &&
+         a.slot_bounds.size() == b.slot_bounds.size() && a.unions.size() == b.unions.size() &&
+         eq(a.rec.data(), b.rec.data(), a.rec.size() * 4) && eq(a.lrec.data(), b.lrec.data(), a.lrec.size() * 4) &&
+         eq(a.nodes.data(), b.nodes.data(), a.nodes.size() * sizeof(fr::BvhNode)) &&
+         eq(a.slot_bounds.data(), b.slot_bounds.data(), a.slot_bounds.size() * sizeof(fr::RefitBox)) &&
+         eq(a.unions.data(), b.unions.data(), a.unions.size() * sizeof(fr::RefitBox));
+}
+
+// the library's patch of one primitive (render.hip patch_copy + refit.hip scene_patch_kernel)
+void patch(Tables& t, const fr::PackedScene& ps, uint32_t i, const fr_prim& p, float reach) {
+  float rec[16], lrec[16];
+  fr::pack_record(p, rec);
+  fr::leaf_record(rec, lrec);
+  memcpy(&t.rec[16 * static_cast<size_t>(i)], rec, 64);
+  const uint32_t slot = ps.slot_of[i];
+  if (slot == fr::kNoSlot) return;
+  memcpy(&t.lrec[16 * static_cast<size_t>(slot)], lrec, 64);
+  fr::RefitBox b = fr::refit_empty();
+  (void)fr::bvh_prim_bounds(p, reach, &b);
+  t.slot_bounds[slot] = b;
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+  if (argc != 2 && argc != 3) {
+    fprintf(stderr, "usage: refit_check FILE [TABLES]\n");
+    return 2;
+  }
+  std::vector<uint32_t> in;
+  FILE* f = fopen(argv[1], "rb");
+  if (!f) return 2;
+  uint32_t buf[1024];
+  size_t got;
+  while ((got = fread(buf, 4, 1024, f)) > 0) in.insert(in.end(), buf, buf + got);
+  fclose(f);
+  static_assert(sizeof(fr_prim) == 88, "22 words per primitive");
+  if (in.size() < 4) return 2;
+  const uint32_t n = in[0], m = in[1], k = in[2], force = in[3];
+  if (in.size() != 4 + static_cast<size_t>(n) * 22 + static_cast<size_t>(k) * 23 + static_cast<size_t>(m) * 8) return 2;
+  std::vector<fr_prim> prims(n);
+  if (n) memcpy(prims.data(), in.data() + 4, static_cast<size_t>(n) * 88);
+  const uint32_t* edits = in.data() + 4 + static_cast<size_t>(n) * 22;
+  const uint32_t* rays = edits + static_cast<size_t>(k) * 23;
+  for (uint32_t e = 0; e < k; ++e)
+    if (edits[23 * static_cast<size_t>(e)] >= n) return 2;
+
+  const fr::PackedScene ps = fr::pack_scene(prims, force != 0);
+  const unsigned char* blob = ps.bytes.data();
+  const bool tree = ps.facts.bvh_ok && ps.facts.n_segs > 0;
+  const float extent = ps.facts.bvh_extent;
+  const float reach = fr::bvh_origin_reach(extent, ps.facts.bvh_sphere_rmin);
+  const float pad = 1e-4f * extent + 1e-4f;
+  Tables first;
+  first.rec.resize(16 * static_cast<size_t>(n));
+  if (n) memcpy(first.rec.data(), blob + ps.off_rec, 64 * static_cast<size_t>(n));
+  first.lrec.resize(16 * static_cast<size_t>(ps.n_slots));
+  first.order.resize(ps.n_slots);
+  first.nodes.resize(ps.n_nodes);
+  first.slot_bounds.resize(ps.n_slots);
+  first.unions.resize(ps.n_nodes);
+  if (ps.n_slots) {
+    memcpy(first.lrec.data(), blob + ps.off_lrec, 64 * static_cast<size_t>(ps.n_slots));
+    memcpy(first.order.data(), blob + ps.off_bvh_order, 4 * static_cast<size_t>(ps.n_slots));
+    memcpy(first.slot_bounds.data(), blob + ps.off_slot_bounds, sizeof(fr::RefitBox) * ps.n_slots);
+  }
+  if (ps.n_nodes) {
+    memcpy(first.nodes.data(), blob + ps.off_bvh, sizeof(fr::BvhNode) * ps.n_nodes);
+    memcpy(first.unions.data(), blob + ps.off_unions, sizeof(fr::RefitBox) * ps.n_nodes);
+  }
+
+  // the schedule: every node once, after both of its children; and the blob's copy of it
+  uint32_t bad_sched = 0;
+  const fr::RefitSchedule& sched = ps.sched;
+  {
+    std::vector<int> at(ps.n_nodes, -1);
+    if (sched.ids.size() != ps.n_nodes) ++bad_sched;
+    for (size_t q = 0; q < sched.ids.size(); ++q) {
+      const uint32_t id = sched.ids[q];
+      if (id >= ps.n_nodes || at[id] >= 0) {
+        ++bad_sched;
+        continue;
+      }
+      at[id] = static_cast<int>(q);
+      for (uint32_t r : first.nodes[id].ref)
+        if (r < fr::kBvhLeaf && (r >= ps.n_nodes || at[r] < 0)) ++bad_sched;
+    }
+    for (int a : at) bad_sched += a < 0;
+    if (sched.offset[sched.heights] != ps.n_nodes || sched.heights > fr::kBvhStack) ++bad_sched;
+    if (ps.n_nodes && memcmp(blob + ps.off_sched, sched.ids.data(), 4 * sched.ids.size()) != 0) ++bad_sched;
+    const uint32_t* so = reinterpret_cast<const uint32_t*>(blob + ps.off_slot_of);
+    for (uint32_t i = 0; i < n; ++i) {
+      if (so[i] != ps.slot_of[i]) ++bad_sched;
+      if (ps.slot_of[i] != fr::kNoSlot && (ps.slot_of[i] >= ps.n_slots || first.order[ps.slot_of[i]] != i)) ++bad_sched;
+    }
+  }
+
+  // bvh_refit over the unmoved primitives reproduces the builder's nodes
+  uint32_t bad_refit = 0;
+  {
+    std::vector<fr::RefitBox> sb(ps.n_slots);
+    for (uint32_t s = 0; s < ps.n_slots; ++s) {
+      sb[s] = fr::refit_empty();
+      if (!fr::bvh_prim_bounds(prims[first.order[s]], reach, &sb[s])) ++bad_refit;
+    }
+    std::vector<fr::BvhNode> nodes = first.nodes;
+    for (fr::BvhNode& nd : nodes) memset(nd.a, 0xFF, 48);  // (only the references are read)
+    std::vector<fr::RefitBox> unions;
+    fr::bvh_refit(nodes, sched, sb, pad, unions);
+    for (uint32_t q = 0; q < ps.n_nodes; ++q) bad_refit += memcmp(&nodes[q], &first.nodes[q], sizeof(fr::BvhNode)) != 0;
+    if (ps.n_slots && memcmp(sb.data(), first.slot_bounds.data(), sizeof(fr::RefitBox) * ps.n_slots) != 0) ++bad_refit;
+    if (ps.n_nodes && memcmp(unions.data(), first.unions.data(), sizeof(fr::RefitBox) * ps.n_nodes) != 0) ++bad_refit;
+  }
+
+  // the edits, as the library applies them
+  std::vector<fr_prim> moved = prims;
+  Tables t = first;
+  uint32_t patchable = 1;
+  for (uint32_t e = 0; e < k; ++e) {
+    const uint32_t i = edits[23 * static_cast<size_t>(e)];
+    fr_prim p;
+    memcpy(&p, edits + 23 * static_cast<size_t>(e) + 1, 88);
+    moved[i] = p;
+  }
+  for (uint32_t e = 0; e < k; ++e) {
+    const uint32_t i = edits[23 * static_cast<size_t>(e)];
+    const fr_prim& p = moved[i];
+    fr::RefitBox own, at_reach, was;
+    const bool bounded = fr::bvh_prim_bounds(p, -1.0f, &own);
+    if (p.kind != prims[i].kind || p.material != prims[i].material || memcmp(p.color, prims[i].color, 12) != 0 ||
+        memcmp(&p.fuzz, &prims[i].fuzz, 4) != 0 || bounded != fr::bvh_prim_bounds(prims[i], -1.0f, &was))
+      patchable = 0;
+    if (tree) {
+      if (bounded)
+        for (int c = 0; c < 3; ++c)
+          if (!(fabsf(own.lo[c]) <= extent) || !(fabsf(own.hi[c]) <= extent)) patchable = 0;
+      if (fr::bvh_prim_bounds(p, reach, &at_reach) != (ps.slot_of[i] != fr::kNoSlot)) patchable = 0;
+    }
+    patch(t, ps, i, p, reach);
+  }
+  const std::vector<fr::BvhNode> old_nodes = t.nodes;
+  if (tree) fr::bvh_refit(t.nodes, sched, t.slot_bounds, pad, t.unions);
+
+  // where each edited primitive sits in its tree
+  std::vector<uint32_t> parent_of_slot(ps.n_slots, fr::kBvhEnd), leaf_of_slot(ps.n_slots, fr::kBvhEnd),
+      side_of_slot(ps.n_slots, fr::kBvhEnd);
+  if (tree) {
+    const fr::BvhSegment* segs = reinterpret_cast<const fr::BvhSegment*>(blob + ps.off_segs);
+    struct Todo {
+      uint32_t ref, parent, side;
+    };
+    std::vector<Todo> todo;
+    for (uint32_t sg = 0; sg < ps.facts.n_segs; ++sg)
+      if (!segs[sg].plane && segs[sg].root != fr::kBvhEnd) todo.push_back(Todo{segs[sg].root, fr::kBvhEnd, fr::kBvhEnd});
+    while (!todo.empty()) {
+      const Todo d = todo.back();
+      todo.pop_back();
+      if (d.ref < fr::kBvhLeaf) {
+        for (uint32_t c = 0; c < 2; ++c)
+          todo.push_back(Todo{first.nodes[d.ref].ref[c], d.ref, d.parent == fr::kBvhEnd ? c : d.side});
+        continue;
+      }
+      const uint32_t lead = d.ref & ((1u << fr::kBvhSlotBits) - 1u), cnt = ((d.ref >> fr::kBvhSlotBits) & 15u) + 1u;
+      for (uint32_t s = lead; s < lead + cnt && s < ps.n_slots; ++s)
+        parent_of_slot[s] = d.parent, leaf_of_slot[s] = lead, side_of_slot[s] = d.side;
+    }
+  }
+
+  fr::CastTables tb;
+  tb.rec = t.rec.data();
+  tb.lrec = t.lrec.data();
+  tb.order = t.order.data();
+  tb.nodes = t.nodes.data();
+  tb.segs = reinterpret_cast<const fr::BvhSegment*>(blob + ps.off_segs);
+  tb.runs = reinterpret_cast<const uint32_t*>(blob + ps.off_runs);
+  tb.n_runs = ps.n_runs;
+  tb.n_segs = tree ? ps.facts.n_segs : 0u;
+  fr::CastTables stale_tb = tb;
+  stale_tb.nodes = old_nodes.data();
+  const uint32_t* cls = reinterpret_cast<const uint32_t*>(blob + ps.off_cls);
+  const float* att = reinterpret_cast<const float*>(blob + ps.off_att);
+
+  uint32_t mismatch = 0, stale = 0;
+  std::vector<uint32_t> lines(static_cast<size_t>(m) * 12);
+  for (uint32_t q = 0; q < m; ++q) {
+    const uint32_t* w = rays + 8 * static_cast<size_t>(q);
+    const fr::GbRay r = fr::cast_ray(fr::V3{as_f32(w[0]), as_f32(w[1]), as_f32(w[2])}, fr::V3{as_f32(w[4]), as_f32(w[5]), as_f32(w[6])});
+    float closest;
+    int best;
+    fr::cast_walk_list(tb, r, closest, best);
+    const bool fb = fr::cast_fallback(r, fr::cast_cull(r), reach);
+    if (tree && !fb) {
+      float tc;
+      int tbest;
+      uint32_t st = 0;
+      fr::cast_walk_tree(tb, r, tc, tbest, &st);
+      if (tbest != best || bits(tc) != bits(closest)) {
+        if (mismatch < 8) fprintf(stderr, "ray %u: list %d %08x tree %d %08x\n", q, best, bits(closest), tbest, bits(tc));
+        ++mismatch;
+      }
+      fr::cast_walk_tree(stale_tb, r, tc, tbest, &st);
+      if (tbest != best || bits(tc) != bits(closest)) ++stale;
+    }
+    fr::GbPixel p = fr::gb_miss();
+    if (best >= 0) {
+      const fr::CastRec rec{tb.rec + 16 * static_cast<size_t>(best)};
+      const float* a = att + 4 * static_cast<size_t>(best);
+      p = fr::gb_hit(static_cast<uint32_t>(best), bits(rec.w[15]), cls[best], rec, fr::GbF4{a[0], a[1], a[2], a[3]}, r, closest);
+    }
+    const uint32_t line[12] = {fr::gb_id(p.g1), bits(p.g0.w), bits(p.g0.x), bits(p.g0.y), bits(p.g0.z), bits(p.g1.x),
+                               bits(p.g1.y), bits(p.g1.z), bits(p.alb.x), bits(p.alb.y), bits(p.alb.z), fb ? 1u : 0u};
+    memcpy(&lines[12 * static_cast<size_t>(q)], line, sizeof(line));
+  }
+
+  if (argc == 3) {
+    FILE* o = fopen(argv[2], "wb");
+    if (!o) return 2;
+    const uint32_t head[4] = {n, ps.n_slots, ps.n_nodes, 0u};
+    fwrite(head, 4, 4, o);
+    if (!t.rec.empty()) fwrite(t.rec.data(), 4, t.rec.size(), o);
+    if (!t.lrec.empty()) fwrite(t.lrec.data(), 4, t.lrec.size(), o);
+    if (!t.order.empty()) fwrite(t.order.data(), 4, t.order.size(), o);
+    if (!t.nodes.empty()) fwrite(t.nodes.data(), sizeof(fr::BvhNode), t.nodes.size(), o);
+    fclose(o);
+  }
+
+  // moving everything back restores the first tables
+  Tables back = t;
+  for (uint32_t e = 0; e < k; ++e) {
+    const uint32_t i = edits[23 * static_cast<size_t>(e)];
+    patch(back, ps, i, prims[i], reach);
+  }
+  if (tree) fr::bvh_refit(back.nodes, sched, back.slot_bounds, pad, back.unions);
+  const uint32_t bad_restore = same_bytes(back, first) ? 0u : 1u;
+
+  printf("info tree %u nodes %u slots %u heights %u patchable %u refit %u sched %u mismatch %u stale %u restore %u\n",
+         tree ? 1u : 0u, ps.n_nodes, ps.n_slots, sched.heights, patchable, bad_refit, bad_sched, mismatch, stale, bad_restore);
+  for (uint32_t e = 0; e < k; ++e) {
+    const uint32_t i = edits[23 * static_cast<size_t>(e)];
+    const uint32_t s = ps.slot_of[i];
+    if (s == fr::kNoSlot)
+      printf("topo %u ffffffff ffffffff ffffffff ffffffff\n", i);
+    else
+      printf("topo %u %x %x %x %x\n", i, s, leaf_of_slot[s], parent_of_slot[s], side_of_slot[s]);
+  }
+  for (uint32_t q = 0; q < m; ++q) {
+    const uint32_t* l = &lines[12 * static_cast<size_t>(q)];
+    printf("%08x %08x %08x %08x %08x %08x %08x %08x %08x %08x %08x %u\n", l[0], l[1], l[2], l[3], l[4], l[5], l[6], l[7], l[8],
+           l[9], l[10], l[11]);
+  }
+  return bad_refit || bad_sched || mismatch || bad_restore ? 1 : 0;
+}
