@@ -56,9 +56,12 @@ bool prim_bounds(const fr_prim& p, Box3& b, float reach = -1.0f) {
       b.grow(g + 3);
       break;
     case FR_OBB: {
-      // centre +- sum_j |axis_j| * half_j per world axis
+      // centre +- sum_j |axis_j| * |half_j| per world axis. The slab test takes the nearer and the
+      // farther plane of each pair, so a negative half size is hit like its magnitude; summed with its
+      // sign it cancelled the other axes' spans in a frame that is not axis-aligned, and the walk
+      // missed the box (tests/test_refit_edges_host.py, turned_neg_half).
       for (int k = 0; k < 3; ++k) {
-        const float e = fabsf(g[3 + k]) * g[12] + fabsf(g[6 + k]) * g[13] + fabsf(g[9 + k]) * g[14];
+        const float e = fabsf(g[3 + k]) * fabsf(g[12]) + fabsf(g[6 + k]) * fabsf(g[13]) + fabsf(g[9 + k]) * fabsf(g[14]);
         b.lo[k] = g[k] - e;
         b.hi[k] = g[k] + e;
       }

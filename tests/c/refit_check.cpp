@@ -21,8 +21,10 @@
 // then per edit `topo INDEX SLOT LEAF PARENT SIDE` (the first slot of its leaf, the node that
 // references the leaf, which child of its tree's root it lies under; ffffffff: none), then one line
 // per ray as cast_check prints it (the list loop over the edited records). TABLES, if given,
-// receives the edited tables: 4 words (n, slots, nodes, 0), the records, the leaf records, the leaf
-// order and the nodes. Exit status 1 if R, C, M or B is not 0.
+// receives the edited tables: 4 words (n, slots, nodes, format = 1), the records, the leaf records,
+// the leaf order, the nodes, and the two tables the next refit reads: the slots' bounds and the
+// nodes' unions (8 words a row; format 0 ended after the nodes). Exit status 1 if R, C, M or B is
+// not 0.
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -273,12 +275,14 @@ int main(int argc, char** argv) {
   if (argc == 3) {
     FILE* o = fopen(argv[2], "wb");
     if (!o) return 2;
-    const uint32_t head[4] = {n, ps.n_slots, ps.n_nodes, 0u};
+    const uint32_t head[4] = {n, ps.n_slots, ps.n_nodes, 1u};
     fwrite(head, 4, 4, o);
     if (!t.rec.empty()) fwrite(t.rec.data(), 4, t.rec.size(), o);
     if (!t.lrec.empty()) fwrite(t.lrec.data(), 4, t.lrec.size(), o);
     if (!t.order.empty()) fwrite(t.order.data(), 4, t.order.size(), o);
     if (!t.nodes.empty()) fwrite(t.nodes.data(), sizeof(fr::BvhNode), t.nodes.size(), o);
+    if (!t.slot_bounds.empty()) fwrite(t.slot_bounds.data(), sizeof(fr::RefitBox), t.slot_bounds.size(), o);
+    if (!t.unions.empty()) fwrite(t.unions.data(), sizeof(fr::RefitBox), t.unions.size(), o);
     fclose(o);
   }
 

@@ -171,7 +171,7 @@ def build_check(root, out):
 
 def run_check(exe, tmp_path, name, prims, idx, new, o, d, force=False, tables=False):
     """(info dict, topo rows [k, 5], list-loop hit dict of the edited scene, tables dict or None) of
-    refit_check."""
+    refit_check. The tables: records, leaf_records, leaf_order, nodes, slot_bounds, node_unions."""
     path = str(tmp_path / f"{name}.bin")
     rays = np.zeros((len(o), 8), F)
     if len(o):
@@ -195,14 +195,17 @@ def run_check(exe, tmp_path, name, prims, idx, new, o, d, force=False, tables=Fa
                     np.int64).reshape(k, 5)
     rows = np.array([[int(t, 16) for t in line.split()] for line in lines[1 + k:]], np.uint32).reshape(len(o), 12)
     got = {"prim": rows[:, 0].copy(), "t": rows[:, 1].copy().view(F), "normal": np.ascontiguousarray(rows[:, 2:5]).view(F),
-           "position": np.ascontiguousarray(rows[:, 5:8]).view(F), "albedo": np.ascontiguousarray(rows[:, 8:11]).view(F)}
+           "position": np.ascontiguousarray(rows[:, 5:8]).view(F), "albedo": np.ascontiguousarray(rows[:, 8:11]).view(F),
+           "fallback": rows[:, 11] != 0}  # (cast_fallback at the packed reach; CF.same does not read it)
     tabs = None
     if tables:
         w = np.fromfile(tpath, np.uint32)
         n, slots, nodes = int(w[0]), int(w[1]), int(w[2])
+        assert int(w[3]) == 1, f"refit_check TABLES format {int(w[3])}, this reader knows 1"
         at = 4
         tabs = {}
-        for key, rows_, width in (("records", n, 16), ("leaf_records", slots, 16), ("leaf_order", slots, 1), ("nodes", nodes, 16)):
+        for key, rows_, width in (("records", n, 16), ("leaf_records", slots, 16), ("leaf_order", slots, 1), ("nodes", nodes, 16),
+                                  ("slot_bounds", slots, 8), ("node_unions", nodes, 8)):
             tabs[key] = w[at:at + rows_ * width].reshape(rows_, width)
             at += rows_ * width
         assert at == len(w)
