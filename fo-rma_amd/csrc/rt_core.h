@@ -461,9 +461,19 @@ FR_HD bool slab_sym(float lo, float hi) {
   return false;
 #endif
 }
+// |inv| in a register of its own (device; one v_and per axis and segment, the statement being
+// common to every use): with it each distance is an fma with a literal, where |inv| as a source
+// modifier wants the literal in a scalar register, one s_mov per distinct coordinate
+FR_HD float slab_abs_inv(float inv) {
+  float a = __builtin_fabsf(inv);
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm("" : "+v"(a));
+#endif
+  return a;
+}
 // the distance of the plane at c (lo or hi) of an axis, and the axis's near / far distance
 FR_HD float slab_pair_d(float lo, float hi, float c, float inv, float oinv) {
-  return slab_sym(lo, hi) ? fmaf(c, __builtin_fabsf(inv), -oinv) : slab_d(c, inv, oinv);
+  return slab_sym(lo, hi) ? fmaf(c, slab_abs_inv(inv), -oinv) : slab_d(c, inv, oinv);
 }
 FR_HD float slab_near(float lo, float hi, float t0, float t1) { return slab_sym(lo, hi) ? t0 : fmin_num(t0, t1); }
 FR_HD float slab_far(float lo, float hi, float t0, float t1) { return slab_sym(lo, hi) ? t1 : fmax_num(t0, t1); }
@@ -550,6 +560,102 @@ FR_HD bool slab_root(const Slab& s, float t_min, float t_max, float& t) {
 }
 
 FR_HD float comp(V3 v, int k) { return k == 0 ? v.x : (k == 1 ? v.y : v.z); }
+
+// Mirrored box pair. Two boxes that are adjacent in the list, share their
+// slabs on two axes bit for bit and on the third axis AX are each other's reflection about 0:
+// one at [-h2, -h1], the other at [h1, h2], 0 <= h1 < h2 <= kSlabSymMax (they may touch at 0).
+// The scene kernel knows this at compile time (slab_mirror_axis over its constant records).
+//
+// The four plane distances of the axis are, as a set, the same for either sign of inv:
+//   D1 = fma(-h2, |inv|, -oinv)  D2 = fma(-h1, |inv|, -oinv)  D3 = fma(h1, |inv|, -oinv)  D4 = fma(h2, |inv|, -oinv)
+// (c inv for inv < 0 has the operands of (-c) |inv|, sign included, as for the symmetric slab
+// above), and D1 <= D2 <= D3 <= D4 because an fma is monotonic in its product. The box the ray
+// meets first, A, has (near, far) = (D1, D2) on the axis and the other, B, has (D3, D4): the
+// bits that the min / max of each box's two distances give, without the four min / max. A is
+// the box on the negative side when inv's sign bit is clear, else the one on the positive side.
+//
+// One candidate for the two. With g = "t > t_min and tn < tf" of slab_root, without t < t_max:
+//   t_A <= tf_A <= D2 <= D3 <= tn_B <= t_B     when g_A and g_B
+// (a root is tn or tf and tn < tf; min3 / max3 return no more / no less than an argument that
+// is a number). So in list order, whichever of the two comes first:
+//   - g_A and t_A < t_max: A is accepted. B is accepted before or after it only with
+//     t_B < t_A, which cannot be, or, when B is first in the list, replaced by A only if
+//     t_A < t_B strictly. The winner is A, except that equal roots leave the list's first box.
+//   - g_A and not t_A < t_max: B fails too, t_B >= t_A.
+//   - not g_A: B alone.
+// Hence t = g_A ? t_A : t_B, hit = (g_A or g_B) and t < t_max, and the winner is the list's
+// second box iff (A is second and g_A and not (g_B and t_A == t_B)) or (A is first and not
+// g_A); the code forms the complement, "the first box wins", without complementing a mask. Equal
+// accepted roots are above t_min, not zeros: the same bits.
+//
+// When the four D are not all numbers:
+//   - h2 |inv| <= 2^27 2^100 is finite, so a D is NaN only through oinv, which all four share:
+//     all NaN, as both boxes' distances are in list order. Then both boxes have the same tn and
+//     tf from the other axes (the NaN-ignoring max3 / min3 skip the axis in both forms), t_A and
+//     t_B are the same bits and g_A = g_B: the tie rule leaves the first box, as the strict
+//     t < closest of the second test does.
+//   - oinv = +-inf: the four D are that infinity, equal numbers.
+//   - inv = +-0 (d = +-inf): the products are zeros and the four D are -oinv. For numbers
+//     tn_A >= D1 = D2 >= tf_A, so neither box has tn < tf, in either form.
+//   - a zero distance may carry the other sign than minNum / maxNum would pick; neither the
+//     root selection nor the face test sees it (as for the symmetric slab).
+// The plane at h1 = 0 goes through slab_d like any plane at 0. h1 = h2 (a flat box) is excluded.
+template <int AX>
+FR_HD bool slab_pair_root(V3 lo, V3 hi, V3 oinv, V3 inv, float t_min, float t_max, float& t, bool& first) {
+  // lo, hi: the list's first box, the second one is its mirror image on AX; first: the winner
+  // is the list's first box
+  const float cl = comp(lo, AX), ch = comp(hi, AX);
+  const bool first_low = ch <= 0.0f;  // the first box is the one on the negative side
+  const float h1 = first_low ? -ch : cl, h2 = first_low ? -cl : ch;
+  const float ai = slab_abs_inv(comp(inv, AX)), noi = -comp(oinv, AX);
+  const float d1 = fmaf(-h2, ai, noi), d4 = fmaf(h2, ai, noi);
+  const float d2 = h1 == 0.0f ? slab_d(0.0f, comp(inv, AX), comp(oinv, AX)) : fmaf(-h1, ai, noi);
+  const float d3 = h1 == 0.0f ? d2 : fmaf(h1, ai, noi);
+  // the two shared axes as slab3_fused forms them; AX's entries are replaced below
+  const float x0 = slab_pair_d(lo.x, hi.x, lo.x, inv.x, oinv.x), x1 = slab_pair_d(lo.x, hi.x, hi.x, inv.x, oinv.x);
+  const float y0 = slab_pair_d(lo.y, hi.y, lo.y, inv.y, oinv.y), y1 = slab_pair_d(lo.y, hi.y, hi.y, inv.y, oinv.y);
+  const float z0 = slab_pair_d(lo.z, hi.z, lo.z, inv.z, oinv.z), z1 = slab_pair_d(lo.z, hi.z, hi.z, inv.z, oinv.z);
+  const float nx = AX == 0 ? 0.0f : slab_near(lo.x, hi.x, x0, x1), fx = AX == 0 ? 0.0f : slab_far(lo.x, hi.x, x0, x1);
+  const float ny = AX == 1 ? 0.0f : slab_near(lo.y, hi.y, y0, y1), fy = AX == 1 ? 0.0f : slab_far(lo.y, hi.y, y0, y1);
+  const float nz = AX == 2 ? 0.0f : slab_near(lo.z, hi.z, z0, z1), fz = AX == 2 ? 0.0f : slab_far(lo.z, hi.z, z0, z1);
+  const float tn_a = fmax3_num(AX == 0 ? d1 : nx, AX == 1 ? d1 : ny, AX == 2 ? d1 : nz);
+  const float tf_a = fmin3_num(AX == 0 ? d2 : fx, AX == 1 ? d2 : fy, AX == 2 ? d2 : fz);
+  const float tn_b = fmax3_num(AX == 0 ? d3 : nx, AX == 1 ? d3 : ny, AX == 2 ? d3 : nz);
+  const float tf_b = fmin3_num(AX == 0 ? d4 : fx, AX == 1 ? d4 : fy, AX == 2 ? d4 : fz);
+  const float t_a = tn_a > t_min ? tn_a : tf_a, t_b = tn_b > t_min ? tn_b : tf_b;
+  const bool g_a = (t_a > t_min) & (tn_a < tf_a), g_b = (t_b > t_min) & (tn_b < tf_b);
+  // A is the list's second box: the ray goes down (sign bit of inv) and the first box is the
+  // lower one, or up and the first is the upper one. One sign compare, and no complement of a
+  // mask: with T = g_b and t_a == t_b, A is used iff g_a and not (sec and T), and the winner is
+  // the list's first box iff (A is used) != sec, that is g_a != sec != (g_a and sec and T).
+  const int ib = __builtin_bit_cast(int, comp(inv, AX));
+  const bool sec = first_low ? ib < 0 : ib >= 0;
+  const bool tie = g_b & (t_a == t_b);
+  t = g_a ? t_a : t_b;
+  first = (g_a != sec) != ((g_a & sec) & tie);
+  return (g_a | g_b) & (t < t_max);
+}
+// The axis on which box j is box i's mirror image in the sense above, or -1: for
+// compile-time records (a constant expression).
+constexpr bool slab_same_bits(float a, float b) {
+  return __builtin_bit_cast(uint32_t, a) == __builtin_bit_cast(uint32_t, b);
+}
+constexpr bool slab_mirrored(float lo_i, float hi_i, float lo_j, float hi_j) {
+  // i below j or j below i; bounds as numbers (a NaN fails every comparison)
+  return lo_j == -hi_i && hi_j == -lo_i && lo_i < hi_i &&
+         ((hi_i <= 0.0f && -lo_i <= kSlabSymMax) || (lo_i >= 0.0f && hi_i <= kSlabSymMax));
+}
+constexpr int slab_mirror_axis(const float (&lo_i)[3], const float (&hi_i)[3], const float (&lo_j)[3],
+                               const float (&hi_j)[3]) {
+  int axis = -1, same = 0;
+  for (int k = 0; k < 3; ++k) {
+    if (slab_same_bits(lo_i[k], lo_j[k]) && slab_same_bits(hi_i[k], hi_j[k]))
+      ++same;
+    else if (slab_mirrored(lo_i[k], hi_i[k], lo_j[k], hi_j[k]))
+      axis = k;
+  }
+  return same == 2 ? axis : -1;
+}
 
 FR_HD V3 axis_normal(int k, float s) {
   return V3{k == 0 ? s : 0.0f, k == 1 ? s : 0.0f, k == 2 ? s : 0.0f};

@@ -456,6 +456,21 @@ struct JitRec {
                        __builtin_bit_cast(float, kJitRec[I][4 * k + 3]));
   }
 };
+// The axis on which boxes i and i + 1 are a mirrored pair that starts at i (slab_mirror_axis,
+// rt_core.h), else -1. Pairs are taken greedily from the front of the list and do not overlap:
+// box i + 1 of a pair starts none.
+constexpr int jit_pair_axis(uint32_t i) {
+  if (i + 1u >= FR_JIT_N || kJitRec[i][15] != FR_AABB || kJitRec[i + 1u][15] != FR_AABB) return -1;
+  if (i > 0u && jit_pair_axis(i - 1u) >= 0) return -1;
+  float lo_i[3] = {}, hi_i[3] = {}, lo_j[3] = {}, hi_j[3] = {};
+  for (int k = 0; k < 3; ++k) {
+    lo_i[k] = __builtin_bit_cast(float, kJitRec[i][k]);
+    hi_i[k] = __builtin_bit_cast(float, kJitRec[i][4 + k]);
+    lo_j[k] = __builtin_bit_cast(float, kJitRec[i + 1u][k]);
+    hi_j[k] = __builtin_bit_cast(float, kJitRec[i + 1u][4 + k]);
+  }
+  return slab_mirror_axis(lo_i, hi_i, lo_j, hi_j);
+}
 #endif
 
 // amdgpu_num_sgpr caps the scalar registers (MI355X_MICROARCH.md "Residency and
@@ -1262,7 +1277,26 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(FR_NUM_SGPR)
         auto test_j = [&](auto ic) {
           constexpr uint32_t I = decltype(ic)::value;
           constexpr uint32_t K = kJitRec[I][15];
-          if constexpr (K == FR_AABB || K == FR_SPHERE || K == FR_PLANE || K == FR_TRIANGLE || K == FR_OBB) {
+          if constexpr (jit_pair_axis(I) >= 0) {
+            // boxes I and I + 1 are mirror images on one axis: one test in ray order and one
+            // update at their place in the list (slab_pair_root, rt_core.h)
+            float t = 0.0f;
+            bool first = false;
+            const JitRec<I> r4{};
+            constexpr int AX = jit_pair_axis(I);
+            const bool h = slab_pair_root<AX>(xyz(r4[0]), xyz(r4[1]), boinv, inv, 0.001f, closest, t, first);
+            // selects, not a branch: the hit tests stay one basic block
+            closest = h ? t : closest;
+            best = h ? static_cast<int>(I + 1u) : best;
+            best = (h & first) ? static_cast<int>(I) : best;
+            if (HAS_PLANE) t_last = h ? t : t_last;
+#if defined(__HIP_DEVICE_COMPILE__)
+            asm volatile("" : "+v"(best));
+            if (HAS_PLANE) asm volatile("" : "+v"(t_last));
+#endif
+          } else if constexpr (I > 0u && jit_pair_axis(I - 1u) >= 0) {
+            // tested with box I - 1
+          } else if constexpr (K == FR_AABB || K == FR_SPHERE || K == FR_PLANE || K == FR_TRIANGLE || K == FR_OBB) {
             test_rec(std::integral_constant<uint32_t, K>{}, I, JitRec<I>{});
           }
           // FR_STUB: never hits (aabb.rs:21-34, rectangle.rs:21-34)
